@@ -17,7 +17,19 @@ Other lines (--workload): gol (config 2), gol_amr, poisson
 of 1-B and 4-B payloads, game of life on the 4-B state, one half-shift
 repartition).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing more: set up,
+warm up, time the K steps, write the outputs if asked, print the JSON line.
+--full adds the figures that take runs of their own: the CPU baseline (the
+oracle on the host cores), the device neighbor build, the halo exchange
+alone (N > 1, and the 1-B / 4-B exchanges of the scalability line) and the
+repartition of the scalability line.  --dump-outputs DIR writes what the
+timed path computed in its last step (the field a caller would read back:
+density, is_alive or solution of the local cells, in cell-id order, a fixed
+seeded sample of them when larger than the budget) as DIR/<name>.npy; the
+inputs are the same from run to run, so two builds can be compared output
+for output.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, this process is only
 a launcher: it starts N rank processes of this script (RANK / LOCAL_RANK /
@@ -54,7 +66,12 @@ def parse(argv=None):
     p.add_argument("--base", type=int, default=None,
                    help="level-0 cells per dimension per GPU (default 128; poisson 384)")
     p.add_argument("--max-ref-lvl", type=int, default=2)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: CPU baseline, neighbor build, "
+                        "halo exchange alone, repartition")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's result as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--workload", choices=["advection", "advection_adapt", "gol", "gol_amr", "poisson",
                                           "scalability"],
@@ -259,6 +276,39 @@ def timed(g, torch, dist, world, fn, steps):
     return el, kms, kn
 
 
+def want_cpu_baseline(a, world):
+    return a.full and not a.no_cpu_baseline and world == 1
+
+
+DUMP_BUDGET = 48 << 20  # bytes of all dumped arrays together (the limit is 64 MB)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(a, g, rank, world, fields):
+    """--dump-outputs: {name: field} read back over the local cells after the
+    last timed step, ordered by cell id (slot order is an implementation
+    detail), cast to float32 (integer states) or float64, and written as
+    DIR/<name>.npy (DIR/<name>.rank<r>.npy for N > 1).  An array above its
+    share of the budget is cut to a fixed seeded sample of the id-ordered
+    cells, the same from run to run."""
+    if not a.dump_outputs:
+        return
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    n = g.n_local
+    order = np.argsort(g.slot_ids()[:n], kind="stable")
+    for name, f in fields.items():
+        v = np.asarray(f.get(0, n))
+        v = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+        keep = DUMP_BUDGET // len(fields) // v.dtype.itemsize
+        if n > keep:
+            pick = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=keep))
+            v = v[order[pick]]
+        else:
+            v = v[order]
+        tag = f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"
+        np.save(os.path.join(a.dump_outputs, tag), v)
+
+
 # ---------------------------------------------------------------------------- game of life (config 2)
 def gol_main(a, dccrgx_mod, torch, dist, rank, world, uid):
     """BASELINE config 2: game of life 1024 x 1024 x 64 (x N, z slabs),
@@ -280,6 +330,7 @@ def gol_main(a, dccrgx_mod, torch, dist, rank, world, uid):
     for _ in range(a.warmup):
         step()
     el, kms, kn = timed(g, torch, dist, world, step, a.steps)
+    dump_outputs(a, g, rank, world, {"is_alive": st})
     n = g.n_local
     mx, sm = reduce_stats(torch, dist, world, [el, float(n), kms])
     ach = 8.0 * n * a.steps / (kms / 1e3) / 1e9
@@ -292,7 +343,7 @@ def gol_main(a, dccrgx_mod, torch, dist, rank, world, uid):
                             "frac": ach / PEAK_HBM_GBS, "traffic": measured_traffic("gol", n, 8 * n, world),
                             "kernel": "gol_structured_yr<2, 2> (gol_structured_v3 with two rows per wave)",
                             "alg_bytes_per_step": 8 * n, "kernel_ms_per_step": kms / a.steps}
-        line["cpu_baseline"] = None if (a.no_cpu_baseline or world > 1) else cpu_baseline("gol", a.cpu_seconds)
+        line["cpu_baseline"] = cpu_baseline("gol", a.cpu_seconds) if want_cpu_baseline(a, world) else None
         print(json.dumps(line), flush=True)
     g.close()
 
@@ -334,6 +385,7 @@ def gol_amr_main(a, dccrgx_mod, torch, dist, rank, world, uid):
     for _ in range(a.warmup):
         g.get_live_neighbors(st, ls)
     el, kms, kn = timed(g, torch, dist, world, lambda: g.get_live_neighbors(st, ls), a.steps)
+    dump_outputs(a, g, 0, 1, {"is_alive": st})
     nl = g.n_local
     total = nl
     kbar = g.neighbor_entries("of") / nl
@@ -369,7 +421,7 @@ def gol_amr_main(a, dccrgx_mod, torch, dist, rank, world, uid):
                         "model_bytes_per_leaf": per_cell, "model": "SURVEY 8(d) GoL CSR/AMR: 8 + 4 k + 4",
                         "model_throughput_GBs": model, "frac_model": model / PEAK_HBM_GBS if model else None,
                         "kernel_ms_per_step": kms / a.steps, "launches_per_step": kn / a.steps}
-    line["cpu_baseline"] = None if a.no_cpu_baseline else cpu_baseline("gol_amr", a.cpu_seconds)
+    line["cpu_baseline"] = cpu_baseline("gol_amr", a.cpu_seconds) if want_cpu_baseline(a, world) else None
     print(json.dumps(line), flush=True)
     g.close()
 
@@ -411,6 +463,7 @@ def gol_amr_partitioned(a, dccrgx_mod, torch, dist, rank, world, uid, n):
     for _ in range(a.warmup):
         step()
     el, kms, kn = timed(g, torch, dist, world, step, a.steps)
+    dump_outputs(a, g, rank, world, {"is_alive": st})
     nl = g.n_local
     kbar = g.neighbor_entries("of") / nl
     per_cell = 8 + 4 * kbar + 4
@@ -478,6 +531,7 @@ def poisson_main(a, dccrgx_mod, torch, dist, rank, world, uid):
     res = {}
     el, kms, kn = timed(g, torch, dist, world, lambda: res.update(r=solver.solve(ids, g, cache_is_up_to_date=True)), 1)
     it, resid = res["r"]
+    dump_outputs(a, g, rank, world, {"solution": sol})
     n_solve = ids.size
     mx, sm = reduce_stats(torch, dist, world, [el, float(n_solve), kms])
     # SURVEY §8(d) 3-phase minimum (34 fp64 accesses) + the 24-B face table read by
@@ -499,7 +553,7 @@ def poisson_main(a, dccrgx_mod, torch, dist, rank, world, uid):
                             "kernel": "po_phase_a + po_reduce + po_phase_b + po_reduce + po_phase_c",
                             "alg_bytes_per_cell_iteration": per_cell, "kernel_ms_per_step": kms / it,
                             "timed_intervals_per_step": kn / it, "residual_min": resid}
-        line["cpu_baseline"] = None if (a.no_cpu_baseline or world > 1) else cpu_baseline("poisson", a.cpu_seconds)
+        line["cpu_baseline"] = cpu_baseline("poisson", a.cpu_seconds) if want_cpu_baseline(a, world) else None
         print(json.dumps(line), flush=True)
     g.close()
 
@@ -534,6 +588,7 @@ def scalability_main(a, dccrgx_mod, torch, dist, rank, world, uid):
     for _ in range(a.warmup):
         step()
     el, kms, kn = timed(g, torch, dist, world, step, a.steps)
+    dump_outputs(a, g, rank, world, {"is_alive": st})
     n = g.n_local
 
     def halo_time(fields_on):
@@ -542,26 +597,29 @@ def scalability_main(a, dccrgx_mod, torch, dist, rank, world, uid):
         e, _, _ = timed(g, torch, dist, world, g.update_copies_of_remote_neighbors, a.steps)
         return e / a.steps
 
-    h4 = halo_time([st])
-    h1 = halo_time([b1])
-    st.set_transfer(True)
-    b1.set_transfer(False)
+    h4 = h1 = rep = 0.0
+    moved = 0
     n_send = g.get_number_of_update_send_cells()
     peers = len(g.get_peers())
-    # one repartition: the first half of every rank's cells to the previous rank
-    loc = g.local_cells()
-    half = loc[: loc.size // 2]
-    dest = np.full(half.size, (rank - 1) % world, np.int32)
-    g.synchronize()
-    if world > 1:
-        dist.barrier()
-    t0 = time.perf_counter()
-    g.balance_load_to(half, dest)
-    g.synchronize()
-    if world > 1:
-        dist.barrier()
-    rep = time.perf_counter() - t0
-    moved = int(half.size) if world > 1 else 0
+    if a.full:
+        h4 = halo_time([st])
+        h1 = halo_time([b1])
+        st.set_transfer(True)
+        b1.set_transfer(False)
+        # one repartition: the first half of every rank's cells to the previous rank
+        loc = g.local_cells()
+        half = loc[: loc.size // 2]
+        dest = np.full(half.size, (rank - 1) % world, np.int32)
+        g.synchronize()
+        if world > 1:
+            dist.barrier()
+        t0 = time.perf_counter()
+        g.balance_load_to(half, dest)
+        g.synchronize()
+        if world > 1:
+            dist.barrier()
+        rep = time.perf_counter() - t0
+        moved = int(half.size) if world > 1 else 0
     mx, sm = reduce_stats(torch, dist, world, [el, float(n), kms, h4, h1, rep, float(n_send), float(moved)])
     if rank == 0:
         line = line_base("cell-updates/s, scalability (BASELINE config 5): game of life + halo on 134M cells/GPU",
@@ -577,18 +635,18 @@ def scalability_main(a, dccrgx_mod, torch, dist, rank, world, uid):
                             "traffic": measured_traffic("scalability", n, 8 * n, world),
                             "kernel": "gol_structured_yr<2, 2> (plane boxes)", "alg_bytes_per_step": 8 * n,
                             "kernel_ms_per_step": kms / a.steps}
-        halo = {"ms_per_exchange_4B": mx[3] * 1e3, "ms_per_exchange_1B": mx[4] * 1e3,
-                "send_cells_max_rank": mx[6], "peers_rank0": peers}
-        if world > 1 and mx[3] > 0:
-            per_link = mx[6] * 4 / max(peers, 1) / mx[3] / 1e9
-            halo["xgmi_4B"] = {"achieved": per_link, "peak": XGMI_LINK_GBS, "unit": "GB/s per link per direction",
-                               "frac": per_link / XGMI_LINK_GBS}
+        halo = {"send_cells_max_rank": mx[6], "peers_rank0": peers}
+        if a.full:
+            halo.update(ms_per_exchange_4B=mx[3] * 1e3, ms_per_exchange_1B=mx[4] * 1e3)
+            if world > 1 and mx[3] > 0:
+                per_link = mx[6] * 4 / max(peers, 1) / mx[3] / 1e9
+                halo["xgmi_4B"] = {"achieved": per_link, "peak": XGMI_LINK_GBS,
+                                   "unit": "GB/s per link per direction", "frac": per_link / XGMI_LINK_GBS}
+            line["repartition"] = {"seconds": mx[5], "cells_moved_total": sm[7],
+                                   "what": "balance_load_to: first half of every rank's cells to the previous rank "
+                                           "(payload migration + distributed ghost refresh + full rebuild)"}
         line["halo"] = halo
-        line["repartition"] = {"seconds": mx[5], "cells_moved_total": sm[7],
-                               "what": "balance_load_to: first half of every rank's cells to the previous rank "
-                                       "(payload migration + distributed ghost refresh + full rebuild)"}
-        line["cpu_baseline"] = None if (a.no_cpu_baseline or world > 1) else cpu_baseline("scalability",
-                                                                                          a.cpu_seconds)
+        line["cpu_baseline"] = cpu_baseline("scalability", a.cpu_seconds) if want_cpu_baseline(a, world) else None
         print(json.dumps(line), flush=True)
     g.close()
 
@@ -647,6 +705,7 @@ def advection_adapt_main(a, dccrg_amd, torch, dist, rank, world, uid):
         reset()
     st.update(cells=0, created=0, removed=0, t_check=0.0, t_adapt=0.0)
     el, kms, kn = timed(g, torch, dist, world, lambda: step(st), a.steps)
+    dump_outputs(a, g, rank, world, {"density": f[0]})
     mx, sm = reduce_stats(torch, dist, world, [el, float(st["cells"]), kms, float(st["created"]),
                                                float(st["removed"]), float(g.n_local)])
     if rank == 0:
@@ -708,11 +767,12 @@ def advection_main(a, dccrg_amd, torch, dist, rank, world, uid):
     for _ in range(a.warmup):
         step()
     el, kern_ms, kern_n = timed(g, torch, dist, world, step, a.steps)
+    dump_outputs(a, g, rank, world, {"density": f[0]})
 
-    # halo break-out (N > 1): the same exchange alone, K times back to back
-    # (pack + grouped RCCL send/recv of the density into the halo slots)
+    # halo break-out (--full, N > 1): the same exchange alone, K times back to
+    # back (pack + grouped RCCL send/recv of the density into the halo slots)
     halo_el = 0.0
-    if world > 1:
+    if a.full and world > 1:
         halo_el, _, _ = timed(g, torch, dist, world, g.update_copies_of_remote_neighbors, a.steps)
     n_send = g.get_number_of_update_send_cells()
     n_peers = len(g.get_peers())
@@ -722,13 +782,15 @@ def advection_main(a, dccrg_amd, torch, dist, rank, world, uid):
     # iterator CSR of the frozen mesh, built once here (the sweep itself uses
     # the face tables); output bytes = 8 B id + 12 B offset + 4 B slot per
     # neighbors_of entry, 8 B per neighbors_to entry, 4 B per iterator entry
-    g.synchronize()
-    tb = time.perf_counter()
-    n_of = g.neighbor_entries("of")
-    g.synchronize()
-    build_s = time.perf_counter() - tb
-    n_to = g.neighbor_entries("to")
-    n_it = g.neighbor_entries("iterator")
+    # (--full only: the timed step never needs it)
+    if a.full:
+        g.synchronize()
+        tb = time.perf_counter()
+        n_of = g.neighbor_entries("of")
+        g.synchronize()
+        build_s = time.perf_counter() - tb
+        n_to = g.neighbor_entries("to")
+        n_it = g.neighbor_entries("iterator")
 
     mx, sm = reduce_stats(torch, dist, world, [el, float(n_local), float(c["recv"]), kern_ms, halo_el, float(n_send)])
     el_max, total_cells = mx[0], int(sm[1])
@@ -769,13 +831,14 @@ def advection_main(a, dccrg_amd, torch, dist, rank, world, uid):
             else None,
             "kernel_ms_per_step": kern_ms / a.steps if a.steps else None,
             "timed_intervals_per_step": kern_n / a.steps if a.steps else 0}
-        line["cpu_baseline"] = None if (a.no_cpu_baseline or world > 1) else cpu_baseline("advection", a.cpu_seconds)
-        line["neighbor_build"] = {
-            "what": "neighbors_of + neighbors_to + iterator CSR of all local cells (device kernels)",
-            "seconds": build_s, "cells_per_s": n_local / build_s if build_s > 0 else None,
-            "entries_of": n_of, "entries_to": n_to,
-            "output_GB_per_s": (24 * n_of + 8 * n_to + 4 * n_it) / build_s / 1e9 if build_s > 0 else None}
-        if world > 1:
+        line["cpu_baseline"] = cpu_baseline("advection", a.cpu_seconds) if want_cpu_baseline(a, world) else None
+        if a.full:
+            line["neighbor_build"] = {
+                "what": "neighbors_of + neighbors_to + iterator CSR of all local cells (device kernels)",
+                "seconds": build_s, "cells_per_s": n_local / build_s if build_s > 0 else None,
+                "entries_of": n_of, "entries_to": n_to,
+                "output_GB_per_s": (24 * n_of + 8 * n_to + 4 * n_it) / build_s / 1e9 if build_s > 0 else None}
+        if a.full and world > 1:
             # rank with the most halo traffic; xGMI: one link per peer pair,
             # ~153 GB/s per link and direction
             halo_ms = mx[4] / a.steps * 1e3

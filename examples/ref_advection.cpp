@@ -10,8 +10,8 @@
 // include path and includes its cell.hpp, initialize.hpp, solve.hpp and
 // adapter.hpp unmodified; their "dccrg.hpp" resolves to the facade
 // (include/dccrg.hpp).  Nothing of the reference is copied into the repo;
-// __graft_entry__.build_examples() compiles this only where /root/reference
-// exists and only the binary (examples/bin/ref_advection) travels.
+// oracle/ref_programs.py compiles this only where the reference checkout
+// exists and only the binary (oracle/_ref/ref_advection) travels.
 //
 // usage: mpiexec -n P ref_advection nx ny nz max_ref_lvl steps out_prefix [balance]
 //   writes <out_prefix>.prerefined.<rank> (after pre-refinement and the last

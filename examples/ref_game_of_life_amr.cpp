@@ -10,8 +10,8 @@
 // tests/game_of_life directory on the include path and includes its cell.hpp,
 // initialize.hpp, refine.hpp and solve.hpp unmodified; their "dccrg.hpp"
 // resolves to the facade (include/dccrg.hpp).  Nothing of the reference is
-// copied into the repo; __graft_entry__.build_examples() compiles this only
-// where /root/reference exists and only the binary travels.
+// copied into the repo; oracle/ref_programs.py compiles this only where the
+// reference checkout exists and only the binary (oracle/_ref/) travels.
 //
 // usage: mpiexec -n P ref_game_of_life_amr direction steps out_prefix
 //   writes <out_prefix>.<step>.<rank> for every turn: {uint64 magic, uint64 n}

@@ -4,13 +4,14 @@
 # every workload.  Usage: scripts/gpu_rehearse.sh TAG [N]
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+export OUT=${OUT:-out}  # where the bench lines go
+mkdir -p "$OUT"
 TAG=${1:-reh}
 N=${2:-2}
 for w in ${WORKLOADS:-advection gol gol_amr poisson scalability advection_adapt}; do
-  DCCRG_BENCH_TRANSPORT=host timeout -k 10 400 python -u bench.py --gpus $N --steps ${STEPS:-5} --warmup 1 --workload $w \
-      > gpurun_out/${TAG}_$w.json 2> gpurun_out/${TAG}_$w.err
+  DCCRG_BENCH_TRANSPORT=host timeout -k 10 400 python -u bench.py --full --gpus $N --steps ${STEPS:-5} --warmup 1 --workload $w \
+      > $OUT/${TAG}_$w.json 2> $OUT/${TAG}_$w.err
   rc=$?
-  echo "[rehearse] $w rc=$rc"; tail -c 600 gpurun_out/${TAG}_$w.json; echo
-  [ $rc -eq 0 ] || { tail -20 gpurun_out/${TAG}_$w.err; exit $rc; }
+  echo "[rehearse] $w rc=$rc"; tail -c 600 $OUT/${TAG}_$w.json; echo
+  [ $rc -eq 0 ] || { tail -20 $OUT/${TAG}_$w.err; exit $rc; }
 done

@@ -3,8 +3,8 @@
 1. The reference's own examples/game_of_life.cpp (BASELINE config 1: 500 x
    500 x 1, neighborhood 1, 100 turns, host loops over cell.neighbors_of /
    neighbor.data, the start / wait halo split), compiled against the facade
-   with only its include line changed (examples/bin/ref_game_of_life, built
-   by __graft_entry__.build()), runs under mpiexec at 1 and 2 ranks sharing
+   with only its include line changed (oracle/_ref/ref_game_of_life, built
+   by oracle/ref_programs.py), runs under mpiexec at 1 and 2 ranks sharing
    the GPU (the library's host exchange over MPI).  The facade dumps the
    state the example's rand() produced as it enters turn 1 and the state
    after the last turn (DCCRGX_DUMP_CELLS); the latter must equal the
@@ -23,6 +23,7 @@ from oracle import oracle as O
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "examples", "bin")
+REF_BIN = os.path.join(ROOT, "oracle", "_ref")  # the reference's programs against the facade
 MPIEXEC = "/opt/conda/bin/mpiexec"
 LEN = (500, 500, 1)
 
@@ -36,7 +37,7 @@ def alive0(ids):
 
 
 def mpirun(exe, P, args=(), env=None):
-    path = os.path.join(BIN, exe)
+    path = os.path.join(REF_BIN if exe.startswith("ref_") else BIN, exe)
     if not os.path.exists(path):
         pytest.fail(f"{path} missing: run __graft_entry__.build() first")
     cmd = [MPIEXEC, "-n", str(P), path] + [str(a) for a in args]

@@ -1,8 +1,8 @@
 """Headline parity pinned to the reference's own advection code.
 
-examples/bin/ref_advection is the repo's 2d.cpp-style main compiled against
+oracle/_ref/ref_advection is the repo's 2d.cpp-style main compiled against
 the facade with the reference's tests/advection/{cell,initialize,solve,
-adapter}.hpp included unmodified (__graft_entry__.build_examples()): the
+adapter}.hpp included unmodified (oracle/ref_programs.py): the
 reference's initialize(), check_for_adaptation / adapt_grid (pre-refinement
 to the maximum level, 2d.cpp:258-292), max_time_step and calculate_fluxes /
 apply_fluxes (solve.hpp:44-279) run on the host over the facade's iterators
@@ -33,7 +33,7 @@ from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "examples", "bin", "ref_advection")
+EXE = os.path.join(ROOT, "oracle", "_ref", "ref_advection")
 MPIEXEC = "/opt/conda/bin/mpiexec"
 BASE, R, STEPS = (32, 32, 32), 2, 100  # parity after 100 steps
 NAMES = ("density", "vx", "vy", "vz", "lx", "ly", "lz")
@@ -65,7 +65,7 @@ def load(prefix, stage, P):
 @pytest.fixture(scope="module")
 def ref_runs(tmp_path_factory):
     if not os.path.exists(EXE):
-        pytest.fail(f"{EXE} missing: run __graft_entry__.build() where /root/reference exists")
+        pytest.fail(f"{EXE} missing: run __graft_entry__.build() where the reference checkout is present")
     d = tmp_path_factory.mktemp("ref_advection")
     runs = {}
     for P in (1, 2):

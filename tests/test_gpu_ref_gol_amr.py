@@ -1,9 +1,9 @@
 """Refined game of life pinned to the reference's own code.
 
-examples/bin/ref_game_of_life_amr is a repo-owned main in the shape of
+oracle/_ref/ref_game_of_life_amr is a repo-owned main in the shape of
 tests/game_of_life/unrefined2d.cpp that includes the reference's
 tests/game_of_life/{cell,initialize,refine,solve}.hpp unmodified and runs
-through the drop-in facade (built by __graft_entry__.build_examples()): every
+through the drop-in facade (built by oracle/ref_programs.py): every
 turn the reference's Refine::refine (random refines / unrefines), a balance,
 the halo, and its get_live_neighbors (solve.hpp:37-170), checked inside the
 program against an unrefined game.  It dumps, per turn and rank, the mesh and
@@ -23,7 +23,7 @@ import dccrg_amd
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "examples", "bin", "ref_game_of_life_amr")
+BIN = os.path.join(ROOT, "oracle", "_ref", "ref_game_of_life_amr")
 MPIEXEC = "/opt/conda/bin/mpiexec"
 LIST = np.dtype((np.uint64, 8))
 MAGIC = 0x676f6c616d723031
@@ -43,7 +43,7 @@ def _load(prefix, step, P):
 @pytest.mark.parametrize("direction,P", [("z", 1), ("x", 1), ("z", 2), ("y", 2)])
 def test_refined_game_matches_reference_solve(gpu, tmp_path, direction, P):
     if not os.path.exists(BIN):
-        pytest.fail(f"{BIN} missing: run __graft_entry__.build() first")
+        pytest.fail(f"{BIN} missing: run __graft_entry__.build() where the reference checkout is present")
     steps = 25
     prefix = str(tmp_path / "gol")
     r = subprocess.run([MPIEXEC, "-n", str(P), BIN, direction, str(steps), prefix], capture_output=True, text=True,

@@ -1,8 +1,9 @@
 """The reference's own known-answer test programs for the hot path, run
 through the drop-in facade on the GPU.
 
-Each program is compiled from /root/reference by __graft_entry__.build_examples()
-with only its include line rewritten (examples/bin/ref_kat_*); its checks are
+Each program is compiled from the reference checkout by oracle/ref_programs.py
+with only its include line rewritten (oracle/_ref/ref_kat_*, which travels
+with the tree to a machine without the reference); its checks are
 its own: it abort()s or returns non-zero on a wrong answer.  They pin, against
 reference-held assertions rather than the oracle:
   get_cells/test1.cpp            get_cells criteria with user neighborhoods,
@@ -35,7 +36,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "examples", "bin")
+BIN = os.path.join(ROOT, "oracle", "_ref")
 MPIEXEC = "/opt/conda/bin/mpiexec"
 
 KATS = ["get_cells", "proc_bdy_cells", "iterators1", "iterators2", "iterators3", "iterators4", "iterators5",
@@ -49,7 +50,7 @@ CASES = [(k, p) for k in KATS for p in ((2, 3) if k == "get_cells" else (1, 3))]
 def test_reference_kat(gpu, kat, P):
     exe = os.path.join(BIN, "ref_kat_" + kat)
     if not os.path.exists(exe):
-        pytest.fail(f"{exe} missing: run __graft_entry__.build() first")
+        pytest.fail(f"{exe} missing: run __graft_entry__.build() where the reference checkout is present")
     r = subprocess.run([MPIEXEC, "-n", str(P), exe], capture_output=True, text=True, timeout=110)
     out = r.stdout + r.stderr
     assert r.returncode == 0, out[-4000:]
