@@ -718,7 +718,9 @@ static void adv_fields(Grid& g, const int fids[7], const double* f[7]) {
 		Field& F = field(g, fids[k]);
 		DX_REQUIRE(F.elem == 8, "advection fields must be fp64");
 		f[k] = (const double*)F.data.p;
+		g.adv_fids[k] = fids[k];  // (dccrgx_advection_layout reports the sweep of these)
 	}
+	g.adv_fids_valid = true;
 }
 
 // the block minima now in g.dt_part (nb of them) belong to fields fids as
@@ -772,6 +774,75 @@ const double* ensure_nbrec(Grid& g, const int fids[7]) {
 	R.n_slots = g.n_slots;
 	R.valid = true;
 	return R.r.p;
+}
+
+// The per-level length table of the tile sweeps (Grid::LenTable) for the
+// fields fids, or nullptr: the sweeps read the length fields.  The table is
+// l0[d] * (1 / 2^level), the expression of dccrgx_advection_initialize and of
+// advection_adapt's reset pass, so on a Cartesian grid whose length fields
+// were set by either (or by geometry.get_length) every slot's lengths are
+// bitwise its level's row.  That is verified, not assumed: one pass over all
+// slots (remote copies too, the sweeps read them as neighbors) on the compute
+// stream, one flag read back, cached on the tiles, the slot count, l0 and the
+// three fields' ids, write epochs and arrays.  A key found changed at two
+// sweeps in a row means the lengths are rewritten every step: the fields are
+// then read without checking until a sweep finds the key unchanged.
+const double* ensure_len_table(Grid& g, const int fids[7], bool sweep) {
+	Grid::LenTable& L = g.lentab;
+	const auto env1 = [](const char* name) {
+		const char* e = std::getenv(name);  // read per call: tests switch them
+		return e && std::atoi(e) == 1;
+	};
+	const char* lt = std::getenv("DCCRGX_LEN_TABLE");
+	// the default kernels only: the experiment variants never take the table
+#if DCCRGX_FUSED_SWEEP
+	return nullptr;
+#endif
+	if ((lt && std::atoi(lt) == 0) || env1("DCCRGX_NBREC") || env1("DCCRGX_FACE_ONCE") || env1("DCCRGX_REG3"))
+		return nullptr;
+	if (!g.geo_block.empty() || g.n_slots == 0 || !g.tiles_valid) return nullptr;
+	for (int k = 4; k < 7; k++)
+		if (field(g, fids[k]).external) return nullptr;
+	bool same = L.keyed && L.tiles_gen == g.tiles_gen && L.n_slots == g.n_slots;
+	for (int d = 0; d < 3 && same; d++) {
+		const Field& F = field(g, fids[4 + d]);
+		same = L.fid[d] == fids[4 + d] && L.epoch[d] == F.epoch && L.ptr[d] == F.data.p && L.l0[d] == g.l0[d];
+	}
+	if (same) {
+		if (sweep) L.changed = 0;
+		if (L.checked) return L.ok ? L.tab.p : nullptr;
+	} else {
+		for (int d = 0; d < 3; d++) {
+			const Field& F = field(g, fids[4 + d]);
+			L.fid[d] = fids[4 + d];
+			L.epoch[d] = F.epoch;
+			L.ptr[d] = F.data.p;
+			L.l0[d] = g.l0[d];
+		}
+		L.tiles_gen = g.tiles_gen;
+		L.n_slots = g.n_slots;
+		L.keyed = true;
+		L.checked = false;
+		if (sweep && ++L.changed >= 2) return nullptr;
+	}
+	if (!L.tab.p || L.tab_l0[0] != g.l0[0] || L.tab_l0[1] != g.l0[1] || L.tab_l0[2] != g.l0[2]) {
+		double h[96];
+		for (int lvl = 0; lvl < 32; lvl++)
+			for (int d = 0; d < 3; d++) h[3 * lvl + d] = g.l0[d] * (1.0 / double(uint64_t(1) << lvl));
+		L.tab.alloc(96);
+		L.flag.alloc(1);
+		h2d(L.tab.p, h, sizeof(h), g.s_comp);
+		HIP_CHECK(hipStreamSynchronize(g.s_comp));  // h is a local
+		for (int d = 0; d < 3; d++) L.tab_l0[d] = g.l0[d];
+	}
+	const double* f[7];
+	for (int k = 0; k < 7; k++) f[k] = (const double*)field(g, fids[k]).data.p;
+	k_len_check(f, g.slot_lvl.p, g.n_slots, L.tab.p, L.flag.p, g.s_comp);
+	int bad = 1;
+	d2h_small(&bad, L.flag.p, sizeof(int), g.s_comp);
+	L.ok = bad == 0;
+	L.checked = true;
+	return L.ok ? L.tab.p : nullptr;
 }
 
 static void gol_step_impl(Grid& g, Field& f, int region) {
@@ -2563,11 +2634,12 @@ int dccrgx_advection_step(dccrgx_grid* gp, const int fids[7], double dt, int reg
 			// (outside the timed interval: a rebuild happens once per mesh or
 			// field change, not per step)
 			const double* rec = ensure_nbrec(g, fids);
+			const double* len = ensure_len_table(g, fids, true);
 			DX_LAP("step.0_nbrec");
 			k_time_begin(g);
 			// tiles never straddle the inner / outer runs
-			if (s0 < g.n_inner) k_advection_tiles(f, (double*)rho.scratch.p, g, 0, dt, g.s_comp, rec);
-			if (s1 > g.n_inner) k_advection_tiles(f, (double*)rho.scratch.p, g, 1, dt, g.s_comp, rec);
+			if (s0 < g.n_inner) k_advection_tiles(f, (double*)rho.scratch.p, g, 0, dt, g.s_comp, rec, len);
+			if (s1 > g.n_inner) k_advection_tiles(f, (double*)rho.scratch.p, g, 1, dt, g.s_comp, rec, len);
 		} else {
 			// the bands of the check that follows computed by the sweep (with the
 			// last check's parameters), recorded per run for band_cache_ok
@@ -2631,10 +2703,32 @@ int dccrgx_advection_layout(dccrgx_grid* gp, uint64_t out[12]) {
 		// (DCCRGX_NBREC=1, ensure_nbrec)
 		const char* env = std::getenv("DCCRGX_NBREC");
 		const bool rec_off = !(env && std::atoi(env) == 1);
-		const uint64_t per_ext = rec_off ? 40 : 32;
+		uint64_t per_ext = rec_off ? 40 : 32;
 		const uint64_t n_irr_cells = n - out[9], ext_irr = g.total_ext - ext_reg;
-		out[11] = 64 * n + 12 * n_irr_cells + (per_ext + 4) * ext_irr + per_ext * ext_reg + 8 * uint64_t(g.n_fine_faces) +
-		          32 * nt;
+		// with the per-level length table (ensure_len_table, for the fields
+		// last passed to an advection call): an out-of-tile neighbor is its
+		// density and one velocity (+ a level byte in the other tiles), an own
+		// cell 40 B (+ a level byte) instead of 64 B
+		uint64_t own = 64, lvl_byte = 0;
+		if (g.adv_fids_valid && ensure_len_table(g, g.adv_fids, false)) {
+			per_ext = 16;
+			lvl_byte = 1;
+			if (DCCRGX_LEN_OWN) own = 40;
+		}
+		out[11] = own * n + (12 + (own == 40 ? lvl_byte : 0)) * n_irr_cells + (per_ext + lvl_byte + 4) * ext_irr +
+		          per_ext * ext_reg + 8 * uint64_t(g.n_fine_faces) + 32 * nt;
+		return 0;
+	});
+}
+
+int dccrgx_advection_length_source(dccrgx_grid* gp, const int fids[7], int* out) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		DX_REQUIRE(out, "null output");
+		const double* f[7];
+		adv_fields(g, fids, f);
+		ensure_tiles(g);
+		*out = ensure_len_table(g, fids, false) ? 1 : 0;
 		return 0;
 	});
 }
@@ -2660,6 +2754,8 @@ int dccrgx_advection_initialize(dccrgx_grid* gp, const int fids[7]) {
 		// with transfer_all_data = true would deliver (initialize.hpp:80)
 		const auto& ids = slot_ids_host(g);
 		const size_t n = g.n_slots;
+		for (int k = 0; k < 7; k++) g.adv_fids[k] = fids[k];
+		g.adv_fids_valid = true;
 		std::vector<double> a[7];
 		for (auto& v : a) v.resize(n);
 		for (size_t i = 0; i < n; i++) {

@@ -394,7 +394,7 @@ struct PoissonState {
 struct RegTileMeta {
 	uint32_t ts;
 	int32_t nst[6];
-	uint32_t pad;
+	uint32_t pad;  // the tile's refinement level (k_tile_levels)
 };
 
 // Send / receive lists of one neighborhood (recalculate_neighbor_update_
@@ -723,6 +723,32 @@ struct Grid {
 		size_t n_slots = 0;
 		bool valid = false;
 	} nbrec;
+	// Cell lengths from the level (ensure_len_table): on a Cartesian grid the
+	// three length fields hold l0[d] * 2^-level, so the tile sweeps can take
+	// them from a per-level table and a level byte instead of 24 B per cell.
+	// `ok` is the verdict of one device pass that compared every slot's three
+	// lengths bitwise with its level's row, for the key below (tiles, slots,
+	// level-0 lengths, the three fields' ids / write epochs / arrays).
+	struct LenTable {
+		DBuf<double> tab;  // 32 rows of (lx, ly, lz)
+		DBuf<int> flag;
+		double tab_l0[3] = {0, 0, 0};  // the level-0 lengths `tab` holds
+		int fid[3] = {-1, -1, -1};
+		uint64_t epoch[3] = {0, 0, 0};
+		const void* ptr[3] = {nullptr, nullptr, nullptr};
+		uint64_t tiles_gen = 0;
+		size_t n_slots = 0;
+		double l0[3] = {0, 0, 0};
+		bool keyed = false;    // the key above is set
+		bool checked = false;  // `ok` belongs to the key
+		bool ok = false;
+		int changed = 0;  // consecutive sweeps that found the key changed
+	} lentab;
+	DBuf<uint8_t> ext_lvl;  // level of every ext_pk entry's slot (parallel to ext_pk)
+	// the fields last passed to an advection entry point (advection_layout
+	// reports the bytes of the sweep of these fields)
+	int adv_fids[7] = {-1, -1, -1, -1, -1, -1, -1};
+	bool adv_fids_valid = false;
 	std::vector<int> halo_fields;  // fixed-size fields of the halo in flight (written again when it lands)
 	std::map<int, UserHood> uhoods;  // add_neighborhood ids
 	GolAmrTables gola;  // refined game of life: per-mesh tables (gol_amr.hip)
@@ -1004,7 +1030,27 @@ void k_advection(const double* const f[7], double* rho_out, const uint32_t* face
 // tiled advection sweep over the regular and the irregular tiles of one run
 // (run 0 inner, 1 outer: tiles never straddle the two)
 void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int run, double dt, hipStream_t s,
-                       const double* nbrec = nullptr);
+                       const double* nbrec = nullptr, const double* lentab = nullptr);
+// the per-level length table (32 rows of lx, ly, lz) for the sweep of fields
+// fids when every slot's three lengths are bitwise their level's row, checked
+// by one device pass and cached (Grid::LenTable); nullptr - the sweeps read
+// the length fields - otherwise, when a length field is external, a stretched
+// geometry is held, DCCRGX_LEN_TABLE=0, or an experiment variant of the tile
+// kernels is selected.  sweep: the call precedes a sweep (a key found changed
+// at two sweeps in a row backs off to the fields without checking)
+const double* ensure_len_table(Grid& g, const int fids[7], bool sweep);
+// 1 when a slot's lengths differ from its level's row of tab (else 0) into flag
+void k_len_check(const double* const f[7], const uint8_t* slot_lvl, size_t n, const double* tab, int* flag,
+                 hipStream_t s);
+// the level bytes the length-table sweeps read: of every ext_pk entry's slot
+// into ext_lvl, of every regular tile into its record's last word
+void k_tile_levels(const uint8_t* slot_lvl, const uint32_t* ext_pk, size_t n_ext, uint8_t* ext_lvl,
+                   RegTileMeta* regmeta, size_t n_reg, hipStream_t s);
+// own cells' lengths from the table too (0: only the out-of-tile neighbors',
+// the first stage of the change, kept for paired A/Bs)
+#ifndef DCCRGX_LEN_OWN
+#define DCCRGX_LEN_OWN 1
+#endif
 // the neighbor records for the sweep of fields fids (rho vx vy vz lx ly lz),
 // rebuilt when stale; nullptr when a velocity / length field is external
 // (or DCCRGX_NBREC=0): the sweeps then read the fields

@@ -776,6 +776,8 @@ void ensure_tiles(Grid& g) {
 	DX_LAP("tiles.1_build");
 	k_classify_tiles(g.m, g.tstart.p, g.n_tiles_inner, g.n_tiles_outer, g.slot_ids.p, g.face_ell.p, g.tlists, g.tnb,
 	                 g.tregmeta, g.tcount, g.s_comp);
+	g.ext_lvl.alloc(g.total_ext + 1);
+	k_tile_levels(g.slot_lvl.p, g.ext_pk.p, g.total_ext, g.ext_lvl.p, g.tregmeta.p, g.tcount[0] + g.tcount[1], g.s_comp);
 	DX_LAP("tiles.2_classify");
 	// records of the irregular tiles for the pipelined tile kernel
 	const size_t nt = g.n_tiles_inner + g.n_tiles_outer, ni = g.tcount[2] + g.tcount[3];

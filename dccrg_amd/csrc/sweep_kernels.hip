@@ -706,12 +706,25 @@ __global__ void nbrec_kernel(const double* __restrict__ lx, const double* __rest
 __device__ __forceinline__ uint32_t nb_area_row(uint32_t a) { return a == 0 ? 5u : 4u; }
 __device__ __forceinline__ uint32_t nb_one_row(uint32_t a) { return a == 2 ? 5u : 6u; }
 
-template <int MINW, bool REC>
+//
+// LEN: the grid's length fields are bitwise l0[d] * 2^-level (ensure_len_table
+// verified it), LT its per-level table (32 rows of lx, ly, lz, copied to LDS).
+// A regular tile and its neighbor boxes are one level, the record's last
+// word, so the tile's three lengths are block-uniform values from the table:
+// the out-of-tile rows shrink from 30 to 12 (per side the density and the
+// velocity along the side's axis), the side columns' length rows are staged
+// from the table, and (DCCRGX_LEN_OWN) so are the own cells', which leaves
+// four own loads of seven.  The flux expressions read the same LDS rows with
+// the same bits, so the densities are bitwise the field-reading kernel's.
+template <int MINW, bool REC, bool LEN>
 __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs P, double* __restrict__ rho_out,
                                                                          const RegTileMeta* __restrict__ meta,
                                                                          uint32_t ntiles, double dt,
-                                                                         const double* __restrict__ R, size_t nrec) {
+                                                                         const double* __restrict__ R, size_t nrec,
+                                                                         const double* __restrict__ LT) {
 #pragma clang fp contract(off)
+	static_assert(!(REC && LEN), "the length table is for the default kernels only");
+	constexpr bool LOWN = LEN && DCCRGX_LEN_OWN;
 	// rows rho, vx, vy, vz, lx, ly, lz; columns 0..511 the tile's own cells,
 	// 512 + 64 d + (face cell) the out-of-tile neighbor across side d (only
 	// rows rho, lx, ly, lz and the velocity along d's axis are filled), so
@@ -720,11 +733,13 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 	__shared__ double shd[7][W];
 	__shared__ double shg[3][512];  // flux through each cell's +x, +y, +z face
 	__shared__ double shm[3][64];   // flux through the tile's -x, -y, -z boundary faces
+	__shared__ double lt[LEN ? 96 : 1];  // LEN: the per-level lengths
 	const StaticTiles tk(ntiles);
 	const uint32_t t1 = tk.t1;
 	uint32_t t = tk.first();
 	if (t >= t1) return;  // block-uniform
 	const uint32_t tid = threadIdx.x;
+	if (LEN && tid < 96u) lt[tid] = LT[tid];  // (read after the first tile's first barrier)
 	const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63u;
 	const uint32_t l[3] = {(tid & 1u) | ((tid >> 2) & 2u) | ((tid >> 4) & 4u),
 	                       ((tid >> 1) & 1u) | ((tid >> 3) & 2u) | ((tid >> 5) & 4u),
@@ -762,20 +777,27 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 	struct RM {
 		uint32_t ts, rec;
 		__device__ __forceinline__ int32_t nst(uint32_t d) const { return int32_t(word_of(rec, int(1 + d))); }
+		__device__ __forceinline__ uint32_t lvl() const { return word_of(rec, 7) & 31u; }
 	};
 	auto unpack = [&](uint32_t v) { return RM{word_of(v, 0), v}; };
 	auto load = [&](const RM& mt, RegSet& r) {
 		const uint32_t ts = mt.ts;
 		const uint32_t o = (ts + tid) << 3;
 		r.c[0] = ldo(rho, o); r.c[1] = ldo(vx, o); r.c[2] = ldo(vy, o);
-		r.c[3] = ldo(vz, o); r.c[4] = ldo(lx, o); r.c[5] = ldo(ly, o);
-		r.c[6] = ldo(lz, o);
+		r.c[3] = ldo(vz, o);
+		if (!LOWN) {
+			r.c[4] = ldo(lx, o); r.c[5] = ldo(ly, o);
+			r.c[6] = ldo(lz, o);
+		}
 #pragma unroll
 		for (int i = 0; i < 4; i++) {
 			const uint32_t row = w + 8u * uint32_t(i);  // wave-uniform
 			r.e[i] = 0;
-			if (row >= (REC ? 24u : 30u)) continue;
-			const uint32_t d = REC ? row >> 2 : row / 5u, val = REC ? row & 3u : row - 5u * d, a = d >> 1;
+			// LEN: 12 rows (side, 0 rho | 1 the velocity along the side's axis)
+			if (LEN && i >= 2) continue;
+			if (row >= (REC ? 24u : (LEN ? 12u : 30u))) continue;
+			const uint32_t d = REC ? row >> 2 : (LEN ? row >> 1 : row / 5u);
+			const uint32_t val = REC ? row & 3u : (LEN ? 4u * (row & 1u) : row - 5u * d), a = d >> 1;
 			const int32_t st = mt.nst(d);
 			if (st < 0) continue;
 			const uint32_t u = lane & 7u, v = lane >> 3, side = (d & 1u) ? 0u : 7u;
@@ -791,13 +813,28 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 		}
 	};
 	// a loaded tile into LDS (after the barrier that ends the previous tile's reads)
-	auto stage = [&](const RegSet& r) {
+	auto stage = [&](const RegSet& r, const RM& ms) {
+		double tl[3] = {0, 0, 0};  // LEN: the tile's lengths, block-uniform
+		if (LEN) {
+			const uint32_t lv = 3u * ms.lvl();
+			tl[0] = lt[lv]; tl[1] = lt[lv + 1]; tl[2] = lt[lv + 2];
+		}
 #pragma unroll
-		for (int k = 0; k < 7; k++) shd[k][tid] = r.c[k];
+		for (int k = 0; k < 7; k++) shd[k][tid] = LOWN && k >= 4 ? tl[k - 4] : r.c[k];
 #pragma unroll
 		for (int i = 0; i < 4; i++) {
 			const uint32_t row = w + 8u * uint32_t(i);
-			if (REC) {
+			if (LEN) {
+				if (i < 2 && row < 12u) {
+					const uint32_t d = row >> 1, col = 512u + 64u * d + lane;
+					if (row & 1u) {
+						shd[1u + (d >> 1)][col] = r.e[i];
+					} else {
+						shd[0][col] = r.e[i];
+						shd[4][col] = tl[0]; shd[5][col] = tl[1]; shd[6][col] = tl[2];
+					}
+				}
+			} else if (REC) {
 				if (row < 24u) {
 					const uint32_t d = row >> 2, val = row & 3u, a = d >> 1, col = 512u + 64u * d + lane;
 					const uint32_t k = val == 0 ? 0u : (val == 1 ? 4u + a : (val == 2 ? nb_area_row(a) : 1u + a));
@@ -876,7 +913,7 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 	// tile tL, then computed; tS becomes the refilled tile (t1: none)
 	auto body = [&](RegSet& S, RM& mS, uint32_t& tS) {
 		__syncthreads();  // the previous tile's faces have been read from LDS
-		stage(S);
+		stage(S, mS);
 		__syncthreads();
 		const RM mc = mS;
 		if (tL < t1) {
@@ -904,7 +941,7 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 	uint32_t rec = tn < t1 ? tile_record_word(meta, tn, lane) : 0u;  // tile tn's record
 	for (;;) {
 		__syncthreads();  // the previous tile's faces have been read from LDS
-		stage(ra);
+		stage(ra, cur);
 		__syncthreads();
 		const bool more = tn < t1;
 		RM nxt = cur;
@@ -1098,20 +1135,31 @@ struct TileMeta {
 // symmetric, see adv_face_g), so the densities are bitwise the two-sided
 // form's.  Faces to ext cells, finer lists and coarser neighbors are still
 // evaluated by each side.
-template <int MINW, bool REC, bool ONCE>
+//
+// LEN (see advection_regular_pp_kernel): an ext cell's three lengths come
+// from the per-level table LT (in LDS) by its level byte extl[k], an array
+// parallel to ext read coalesced with the ext code; (DCCRGX_LEN_OWN) an own
+// cell's by slvl[slot], a coalesced 1-B load instead of three 8-B ones.  The
+// lengths are put into the same LDS rows with the same bits as the fields'.
+template <int MINW, bool REC, bool ONCE, bool LEN>
 __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
     AdvPtrs P, double* __restrict__ rho_out, const uint32_t* __restrict__ tell, uint32_t tplane,
     const uint32_t* __restrict__ ext, const uint32_t* __restrict__ tfine, const TileMeta* __restrict__ meta,
-    uint32_t ntiles, uint32_t ecap, double dt, const double* __restrict__ R, size_t nrec) {
+    uint32_t ntiles, uint32_t ecap, double dt, const double* __restrict__ R, size_t nrec,
+    const uint8_t* __restrict__ slvl, const uint8_t* __restrict__ extl, const double* __restrict__ LT) {
 #pragma clang fp contract(off)
+	static_assert(!(LEN && (REC || ONCE)), "the length table is for the default kernels only");
+	constexpr bool LOWN = LEN && DCCRGX_LEN_OWN;
 	constexpr uint32_t T = 512;
 	// [7][T + ecap] doubles (rho vx vy vz lx ly lz); ONCE: 3 x T doubles of
-	// +a face fluxes; 2 x T u32 finer-face pairs; ONCE: 3 x T flags
+	// +a face fluxes; 2 x T u32 finer-face pairs; ONCE: 3 x T flags; LEN: 96
+	// doubles, the per-level lengths
 	extern __shared__ double shd[];
 	const uint32_t W = T + ecap;
 	double* shg = shd + 7 * W;
 	uint32_t* shf = reinterpret_cast<uint32_t*>(shd + 7 * W + (ONCE ? 3 * T : 0));
 	uint8_t* shok = reinterpret_cast<uint8_t*>(shf + 2 * T);
+	double* lt = reinterpret_cast<double*>(shf + 2 * T);  // (LEN excludes ONCE)
 	const StaticTiles tk(ntiles);
 	const uint32_t t1 = tk.t1;
 	uint32_t t = tk.first();
@@ -1127,16 +1175,33 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 	// the register set of the tile being loaded (field order rho vx vy vz lx ly lz)
 	double c[7], xa[7], xb[7];
 	uint32_t row[3], fq[2];
+	uint32_t lvc = 0, lva = 0, lvb = 0;  // LEN: the level bytes of c, xa, xb
+	if (LEN && tid < 96u) lt[tid] = LT[tid];  // (read after the first tile's first barrier)
 	auto load7 = [&](uint32_t slot, double (&v)[7]) {
 		const uint32_t o = slot << 3;
 		v[0] = ldo(rho, o); v[1] = ldo(vx, o); v[2] = ldo(vy, o); v[3] = ldo(vz, o);
+		if (LOWN) {
+			lvc = __builtin_nontemporal_load(slvl + slot);
+			return;
+		}
 		v[4] = ldo(lx, o); v[5] = ldo(ly, o); v[6] = ldo(lz, o);
+	};
+	// a cell's lengths from the table by its level byte (at staging time)
+	auto lengths = [&](uint32_t lv, double (&v)[7]) {
+		const uint32_t k = 3u * (lv & 31u);
+		v[4] = lt[k]; v[5] = lt[k + 1]; v[6] = lt[k + 2];
 	};
 	// ext = slot | axis mask << 29: density and lengths, and only the
 	// velocity components along the axes its faces cross
 	auto load5 = [&](uint32_t q, double (&v)[7]) {
 		const uint32_t sl = q & 0x1fffffffu, o = sl << 3, ax = q >> 29;
 		v[0] = ldo(rho, o);
+		if (LEN) {
+			v[1] = (ax & 1u) ? ldo(vx, o) : 0.0;
+			v[2] = (ax & 2u) ? ldo(vy, o) : 0.0;
+			v[3] = (ax & 4u) ? ldo(vz, o) : 0.0;
+			return;
+		}
 		if (REC && (ax == 1u || ax == 2u || ax == 4u)) {
 			// reached through faces of one axis (all but ~0.3 % on config 3):
 			// its density and that axis' record, staged in the rows of
@@ -1176,8 +1241,14 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 			row[1] = __builtin_nontemporal_load(tell + tplane + (ts + tid));
 			row[2] = __builtin_nontemporal_load(tell + 2 * tplane + (ts + tid));
 		}
-		if (tid < ne) load5(__builtin_nontemporal_load(ext + e0 + tid), xa);
-		if (tid + T < ne) load5(__builtin_nontemporal_load(ext + e0 + tid + T), xb);
+		if (tid < ne) {
+			load5(__builtin_nontemporal_load(ext + e0 + tid), xa);
+			if (LEN) lva = __builtin_nontemporal_load(extl + e0 + tid);
+		}
+		if (tid + T < ne) {
+			load5(__builtin_nontemporal_load(ext + e0 + tid + T), xb);
+			if (LEN) lvb = __builtin_nontemporal_load(extl + e0 + tid + T);
+		}
 		if (tid < nf) {
 			typedef unsigned int u2v __attribute__((ext_vector_type(2)));
 			const u2v q = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(tfine) + (fb + tid));
@@ -1192,15 +1263,21 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 	for (;;) {
 		const uint32_t n = cur.n, ne = cur.ne, nf = cur.nf, ts = cur.ts;
 		__syncthreads();  // the previous tile's faces have been read from LDS
-		if (tid < n)
+		if (tid < n) {
+			if (LOWN) lengths(lvc, c);
 #pragma unroll
 			for (int k = 0; k < 7; k++) shd[k * W + tid] = c[k];
-		if (tid < ne)
+		}
+		if (tid < ne) {
+			if (LEN) lengths(lva, xa);
 #pragma unroll
 			for (int k = 0; k < 7; k++) shd[k * W + T + tid] = xa[k];
-		if (tid + T < ne)
+		}
+		if (tid + T < ne) {
+			if (LEN) lengths(lvb, xb);
 #pragma unroll
 			for (int k = 0; k < 7; k++) shd[k * W + 2 * T + tid] = xb[k];
+		}
 		if (tid < nf) {
 			shf[2 * tid] = fq[0];
 			shf[2 * tid + 1] = fq[1];
@@ -2013,7 +2090,7 @@ void k_advection_ell(const double* const f[7], double* rho_out, const int32_t* e
 }
 
 void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int run, double dt, hipStream_t s,
-                       const double* nbrec) {
+                       const double* nbrec, const double* lentab) {
 	const size_t n_reg = g.tcount[run], n_irr = g.tcount[2 + run];
 	const AdvPtrs P{{f[0], f[4], f[5], f[6], f[1], f[2], f[3]}};
 	if (n_irr && !g.tmeta.n) {
@@ -2045,11 +2122,14 @@ void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int r
 		} else {
 			const unsigned nblk = unsigned(std::min<size_t>(size_t(256) * 2, (n_reg + 7) / 8 * 8));
 			if (nbrec)
-				advection_regular_pp_kernel<4, true><<<nblk, 512, 0, s>>>(P, rho_out, meta, uint32_t(n_reg), dt, nbrec,
-				                                                          g.n_slots);
+				advection_regular_pp_kernel<4, true, false><<<nblk, 512, 0, s>>>(P, rho_out, meta, uint32_t(n_reg), dt,
+				                                                                 nbrec, g.n_slots, nullptr);
+			else if (lentab)
+				advection_regular_pp_kernel<4, false, true><<<nblk, 512, 0, s>>>(P, rho_out, meta, uint32_t(n_reg), dt,
+				                                                                 nullptr, 0, lentab);
 			else
-				advection_regular_pp_kernel<4, false><<<nblk, 512, 0, s>>>(P, rho_out, meta, uint32_t(n_reg), dt, nullptr,
-				                                                           0);
+				advection_regular_pp_kernel<4, false, false><<<nblk, 512, 0, s>>>(P, rho_out, meta, uint32_t(n_reg), dt,
+				                                                                  nullptr, 0, nullptr);
 		}
 		HIP_CHECK(hipGetLastError());
 	}
@@ -2061,28 +2141,56 @@ void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int r
 		// more than the halved flux arithmetic)
 		static const char* fo = std::getenv("DCCRGX_FACE_ONCE");
 		const bool once = fo && fo[0] == '1';
+		const bool len = lentab && !nbrec && !once;  // the length table: the default kernel only
 		const size_t lds = size_t(7) * (512 + ecap) * sizeof(double) + size_t(2) * 512 * sizeof(uint32_t) +
-		                   (once ? size_t(3) * 512 * (sizeof(double) + 1) : 0);
+		                   (once ? size_t(3) * 512 * (sizeof(double) + 1) : 0) + (len ? 96 * sizeof(double) : 0);
 		const unsigned nblk = unsigned(std::min<size_t>(size_t(256) * 2, (n_irr + 7) / 8 * 8));
 		const uint32_t tp = uint32_t(g.n_local + 1);
 		if (nbrec && once)
-			advection_tiles_pp_kernel<4, true, true><<<nblk, 512, lds, s>>>(P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p,
-			                                                                meta, uint32_t(n_irr), ecap, dt, nbrec,
-			                                                                g.n_slots);
+			advection_tiles_pp_kernel<4, true, true, false><<<nblk, 512, lds, s>>>(
+			    P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt, nbrec, g.n_slots, nullptr,
+			    nullptr, nullptr);
 		else if (nbrec)
-			advection_tiles_pp_kernel<4, true, false><<<nblk, 512, lds, s>>>(P, rho_out, g.tell.p, tp, g.ext_pk.p,
-			                                                                 g.tfine.p, meta, uint32_t(n_irr), ecap, dt,
-			                                                                 nbrec, g.n_slots);
+			advection_tiles_pp_kernel<4, true, false, false><<<nblk, 512, lds, s>>>(
+			    P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt, nbrec, g.n_slots, nullptr,
+			    nullptr, nullptr);
 		else if (once)
-			advection_tiles_pp_kernel<4, false, true><<<nblk, 512, lds, s>>>(P, rho_out, g.tell.p, tp, g.ext_pk.p,
-			                                                                 g.tfine.p, meta, uint32_t(n_irr), ecap, dt,
-			                                                                 nullptr, 0);
+			advection_tiles_pp_kernel<4, false, true, false><<<nblk, 512, lds, s>>>(
+			    P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt, nullptr, 0, nullptr,
+			    nullptr, nullptr);
+		else if (len)
+			advection_tiles_pp_kernel<4, false, false, true><<<nblk, 512, lds, s>>>(
+			    P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt, nullptr, 0, g.slot_lvl.p,
+			    g.ext_lvl.p, lentab);
 		else
-			advection_tiles_pp_kernel<4, false, false><<<nblk, 512, lds, s>>>(P, rho_out, g.tell.p, tp, g.ext_pk.p,
-			                                                                  g.tfine.p, meta, uint32_t(n_irr), ecap, dt,
-			                                                                  nullptr, 0);
+			advection_tiles_pp_kernel<4, false, false, false><<<nblk, 512, lds, s>>>(
+			    P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt, nullptr, 0, nullptr,
+			    nullptr, nullptr);
 		HIP_CHECK(hipGetLastError());
 	}
+}
+
+// ensure_len_table's check: flag = 1 when a slot's three lengths are not
+// bitwise its level's row of the table
+__global__ void len_check_kernel(const double* __restrict__ lx, const double* __restrict__ ly,
+                                 const double* __restrict__ lz, const uint8_t* __restrict__ lvl, size_t n,
+                                 const double* __restrict__ tab, int* __restrict__ flag) {
+	bool bad = false;
+	for (size_t s = blockIdx.x * size_t(blockDim.x) + threadIdx.x; s < n; s += size_t(gridDim.x) * blockDim.x) {
+		const double* r = tab + 3u * (lvl[s] & 31u);
+		bad |= __double_as_longlong(lx[s]) != __double_as_longlong(r[0]) ||
+		       __double_as_longlong(ly[s]) != __double_as_longlong(r[1]) ||
+		       __double_as_longlong(lz[s]) != __double_as_longlong(r[2]);
+	}
+	if (bad) atomicOr(flag, 1);
+}
+
+void k_len_check(const double* const f[7], const uint8_t* slot_lvl, size_t n, const double* tab, int* flag,
+                 hipStream_t s) {
+	HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), s));
+	if (!n) return;
+	len_check_kernel<<<grid_for(n, 256, 256u * 16u), 256, 0, s>>>(f[4], f[5], f[6], slot_lvl, n, tab, flag);
+	HIP_CHECK(hipGetLastError());
 }
 
 void k_nbrec(const double* const f[7], size_t n, double* r, hipStream_t s) {

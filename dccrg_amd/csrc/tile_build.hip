@@ -925,4 +925,24 @@ void k_classify_tiles(const MapCtx& m, const uint32_t* tstart, size_t n_tiles_in
 	HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// The level bytes of the length-table sweeps (sweep_kernels.hip): entry k of
+// ext_lvl is the level of ext_pk[k]'s slot, read coalesced with the ext code
+// (no gather into slot_lvl during the sweep); a regular tile is one level by
+// construction, its first slot's goes into the record's last word.
+__global__ void tile_levels_kernel(const uint8_t* __restrict__ slot_lvl, const uint32_t* __restrict__ ext_pk,
+                                   size_t n_ext, uint8_t* __restrict__ ext_lvl, RegTileMeta* __restrict__ regmeta,
+                                   size_t n_reg) {
+	const size_t stride = size_t(gridDim.x) * blockDim.x, i0 = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+	for (size_t k = i0; k < n_ext; k += stride) ext_lvl[k] = slot_lvl[ext_pk[k] & 0x1fffffffu] & 31u;
+	for (size_t k = i0; k < n_reg; k += stride) regmeta[k].pad = slot_lvl[regmeta[k].ts] & 31u;
+}
+
+void k_tile_levels(const uint8_t* slot_lvl, const uint32_t* ext_pk, size_t n_ext, uint8_t* ext_lvl,
+                   RegTileMeta* regmeta, size_t n_reg, hipStream_t s) {
+	const size_t n = std::max(n_ext, n_reg);
+	if (!n) return;
+	tile_levels_kernel<<<grid_for(n, 256), 256, 0, s>>>(slot_lvl, ext_pk, n_ext, ext_lvl, regmeta, n_reg);
+	HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace dccrgx

@@ -875,6 +875,14 @@ class Dccrg:
         compute stream: no host round trip over RCCL."""
         check(lib().dccrgx_advection_max_time_step_device(self.h, self._fids(fields), _dev_ptr(out)))
 
+    def advection_length_source(self, fields):
+        """1 when the tile sweeps of `fields` take the cell lengths from the
+        per-level table (verified bitwise against the length fields), 0 when
+        they read the length fields (see include/dccrgx.h)."""
+        v = C.c_int()
+        check(lib().dccrgx_advection_length_source(self.h, self._fids(fields), C.byref(v)))
+        return v.value
+
     def advection_layout(self):
         """Tile layout of the advection sweep and its algorithmic HBM bytes per
         sweep over all local cells (see include/dccrgx.h)."""

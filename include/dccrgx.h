@@ -488,9 +488,24 @@ int dccrgx_advection_adapt(dccrgx_grid* g, const int fields[7], uint64_t out[2])
  * its 12 B of face codes, per out-of-tile neighbor its density, three
  * lengths and the velocity along the face (40 B; 32 B with the experimental
  * neighbor records) plus 4 B of list entry in an irregular tile, 8 B per
- * finer face, 32 B per tile record (ABI 9: out[12]).
+ * finer face, 32 B per tile record (ABI 9: out[12]).  When the sweep of the
+ * fields last passed to an advection call takes the cell lengths from the
+ * per-level table (dccrgx_advection_length_source), [11] counts 40 B per own
+ * cell (41 B in an irregular tile: its level byte) and 16 B per out-of-tile
+ * neighbor (density and the velocity along the face; + its level byte in an
+ * irregular tile); [6] and [7] stay SURVEY's definition.
  * No reference counterpart (roofline introspection). */
 int dccrgx_advection_layout(dccrgx_grid* g, uint64_t out[12]);
+
+/* Where the tile sweeps of fields fids (density, vx, vy, vz, lx, ly, lz) take
+ * the cell lengths from: *out = 1 the per-level table l0[d] * 2^-level (every
+ * slot's three lengths, remote copies included, were compared bitwise with
+ * their level's row by a device pass, cached until the tiles, the geometry or
+ * the length fields change), 0 the length fields (the lengths differ
+ * somewhere, a length field's device pointer is out, a stretched geometry
+ * block is held, or DCCRGX_LEN_TABLE=0).  The densities are bitwise the same
+ * either way.  No reference counterpart. */
+int dccrgx_advection_length_source(dccrgx_grid* g, const int fids[7], int* out);
 
 /* ---- Poisson solver (tests/poisson/poisson_solve.hpp:156-1056) ----------
  * dccrgx_poisson_cache = Poisson_Solve::cache_system_info (827-971): local
