@@ -126,6 +126,8 @@ _SIGS = {
     "dccrgx_variable_field_download": (C.c_int, [vp, C.c_int, sz, sz, vp, sz, P(sz)]),
     "dccrgx_variable_field_device_ptr": (C.c_int, [vp, C.c_int, P(vp), P(vp)]),
     "dccrgx_removed_variable_field_download": (C.c_int, [vp, C.c_int, vp, vp, sz, P(sz)]),
+    "dccrgx_get_existing_cells_at": (C.c_int, [vp, vp, sz, vp]),
+    "dccrgx_particles_step": (C.c_int, [vp, C.c_int, C.c_int, P(C.c_double), C.c_double, P(u64)]),
     "dccrgx_set_send_single_cells": (C.c_int, [vp, C.c_int]),
     "dccrgx_get_send_single_cells": (C.c_int, [vp, P(C.c_int)]),
     "dccrgx_set_field_window": (C.c_int, [vp, C.c_int, sz, sz]),

@@ -2319,6 +2319,24 @@ int dccrgx_removed_variable_field_download(dccrgx_grid* gp, int fid, uint64_t* s
 	});
 }
 
+// ---- particles in cells (tests/particles; particles.hip) ----------------------
+int dccrgx_get_existing_cells_at(dccrgx_grid* gp, const double* xyz, size_t n, uint64_t* ids) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		existing_cells_at(g, xyz, n, ids);
+		return 0;
+	});
+}
+
+int dccrgx_particles_step(dccrgx_grid* gp, int var_field, int record_doubles, const double* velocity, double dt,
+                          uint64_t* stats) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		particles_step(g, var_field, record_doubles, velocity, dt, stats);
+		return 0;
+	});
+}
+
 // cells_to_send / cells_to_receive while a balance_load is in progress
 // (initialize_balance_load fills them with the migration lists, 3746-3884)
 int dccrgx_get_migration_cells(dccrgx_grid* gp, int peer, int incoming, uint64_t* ids, size_t cap, size_t* n) {

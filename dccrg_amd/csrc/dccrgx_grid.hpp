@@ -41,4 +41,10 @@ std::vector<uint64_t> cells_by_criteria(Grid& g, const int32_t* crit, size_t nc,
 int64_t host_slot_of(Grid& g, uint64_t id);
 bool gol_slab_plan(Grid& g, std::vector<GolBox>& inner, std::vector<GolBox>& outer);
 
+// particles.hip: the smallest known leaf at each of n host coordinates
+// (error_cell: none), and one push / locate / re-bin step of a variable field
+// of K-double particle records (stats: stayed, moved, arrived, handed over, lost)
+void existing_cells_at(Grid& g, const double* xyz, size_t n, uint64_t* ids);
+void particles_step(Grid& g, int fid, int K, const double* velocity, double dt, uint64_t stats[5]);
+
 }  // namespace dccrgx

@@ -1,0 +1,540 @@
+// Particles in cells (tests/particles/simple.cpp): a variable field of fp64
+// records (K doubles each, doubles 0..2 the position) is pushed, wrapped
+// through the periodic geometry, located (get_existing_cell(coordinate),
+// dccrg.hpp:6316-6336) and re-binned into the cells' lists on the device.
+//
+// One __device__ function does the point location, a literal restatement of
+// Cartesian_Geometry::get_real_coordinate / get_indices(coordinate)
+// (dccrg_cartesian_geometry.hpp:521-607) and the finest-first probe of
+// get_existing_cell(indices, 0, R) (dccrg.hpp:11275-11308); the batch query
+// and the particle step both call it.
+//
+// The step (DESIGN.md "Particles"):
+//   1. locate  - a thread per particle: source slot (search of the record
+//                offsets, narrowed per block), x' = real(x + v dt) stored
+//                back, destination slot, stay / mover flags, statistics;
+//   2. two exclusive scans (stayers, movers) in one pass of temp storage;
+//   3. movers compacted to (destination slot, rank of the source id | index)
+//                keys and sorted by one stable radix sort;
+//   4. arrivals per destination from the run boundaries of the sorted keys;
+//   5. a scan of the new record counts;
+//   6. scatter - stayers and movers into a fresh pool, swapped in.
+// No atomic decides a position: a cell's records are its stayers in their
+// previous order, then the arrivals ordered by (source cell id, index in the
+// source cell).
+#include <hipcub/hipcub.hpp>
+
+#include <cmath>
+
+#include "dccrgx_grid.hpp"
+
+// x + v dt, x +- L ceil(d / L) and (x - start) / l are separately rounded
+// operations in the reference; hipcc fuses a * b + c by default
+#pragma clang fp contract(off)
+
+namespace dccrgx {
+
+namespace {
+
+// Cartesian geometry of the whole grid: start, end (get_end: start + double(
+// length) * l0, formed on the host), the finest cell's length l0 / 2^R
+struct PGeo {
+	double start[3], end[3], cell[3];
+	int per[3];
+};
+
+PGeo make_geo(const Grid& g) {
+	PGeo G;
+	for (int d = 0; d < 3; d++) {
+		G.start[d] = g.start[d];
+		const double span = double(g.len[d]) * g.l0[d];
+		G.end[d] = g.start[d] + span;
+		G.cell[d] = g.l0[d] / double(uint64_t(1) << g.R);
+		G.per[d] = g.per[d];
+	}
+	return G;
+}
+
+// get_real_coordinate of one dimension (dccrg_cartesian_geometry.hpp:534-561)
+__device__ __forceinline__ double real_coordinate(const PGeo& G, int d, double x) {
+	const double start = G.start[d], end = G.end[d];
+	if (x >= start && x <= end) return x;
+	if (!G.per[d]) return __longlong_as_double(0x7ff8000000000000ll);
+	const double L = end - start;
+	if (x < start) {
+		const double distance = start - x;
+		const double q = distance / L;
+		const double w = L * ceil(q);
+		return x + w;
+	}
+	const double distance = x - end;
+	const double q = distance / L;
+	const double w = L * ceil(q);
+	return x - w;
+}
+
+// dm_owner(M, id) >= 0 without the owner (an implicit mesh: no division)
+__device__ __forceinline__ bool known_leaf(const DevMesh& M, uint64_t id) {
+	if (id == error_cell || id > M.last) return false;
+	if (M.implicit) return id <= M.bp.n0;
+	int32_t o, s;
+	return dm_lookup(M, id, o, s);
+}
+
+// the smallest leaf this process knows at x (error_cell: outside the grid,
+// or nothing known there); get_indices wraps the coordinate once more, as
+// the reference does
+__device__ __forceinline__ uint64_t existing_cell_at(const MapCtx& m, const DevMesh& M, const PGeo& G,
+                                                     const double x[3]) {
+	uint64_t ind[3];
+#pragma unroll
+	for (int d = 0; d < 3; d++) {
+		const double c = real_coordinate(G, d, x[d]);
+		if (!(c >= G.start[d] && c <= G.end[d])) return error_cell;
+		const double rel = c - G.start[d];
+		const double q = rel / G.cell[d];
+		ind[d] = uint64_t(floor(q));
+		// a coordinate at the grid's end is inside for the wrap but indexes one
+		// past the last cell (get_existing_cell(indices), dccrg.hpp:11280-11290)
+		if (ind[d] >= m.glen[d]) return error_cell;
+	}
+	for (int lvl = m.R; lvl >= 0; lvl--) {
+		const uint64_t id = map_from_indices(m, ind[0], ind[1], ind[2], lvl);
+		if (known_leaf(M, id)) return id;
+	}
+	return error_cell;
+}
+
+__global__ void cells_at_kernel(const MapCtx m, const DevMesh M, const PGeo G, const double* __restrict__ xyz, size_t n,
+                                uint64_t* __restrict__ ids) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
+		const double x[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+		ids[i] = existing_cell_at(m, M, G, x);
+	}
+}
+
+constexpr int kPB = 256;         // particles per block pass
+constexpr int kOffCache = 1024;  // record offsets of a block's slots kept in LDS
+
+// first index in [lo, hi) with a[i] > v
+template <class T>
+__device__ __forceinline__ size_t upper_bound_idx(const T* a, size_t lo, size_t hi, T v) {
+	while (lo < hi) {
+		const size_t mid = lo + (hi - lo) / 2;
+		if (a[mid] > v)
+			hi = mid;
+		else
+			lo = mid + 1;
+	}
+	return lo;
+}
+
+// byte offsets -> record offsets; flag: an offset that is no whole record
+__global__ void record_offsets_kernel(const uint64_t* __restrict__ voff, size_t n, uint64_t rec,
+                                      uint32_t* __restrict__ ofirst, int32_t* __restrict__ flag) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
+		const uint64_t q = voff[i] / rec;
+		if (q * rec != voff[i]) *flag = 1;
+		ofirst[i] = uint32_t(q);
+	}
+}
+
+// slot of the first particle of every block pass (and, last entry, of the last particle)
+__global__ void chunk_slots_kernel(const uint32_t* __restrict__ ofirst, size_t n_slots, size_t N, size_t chunks,
+                                   uint32_t* __restrict__ chunk_slot) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i <= chunks; i += size_t(gridDim.x) * blockDim.x) {
+		const size_t p = i < chunks ? i * kPB : N - 1;
+		chunk_slot[i] = uint32_t(upper_bound_idx<uint32_t>(ofirst, 0, n_slots + 1, uint32_t(p)) - 1);
+	}
+}
+
+// (the mapping, the mesh and the geometry are kernel parameters of their own:
+// inside one struct their lane-uniform array reads put the struct in scratch)
+struct PArgs {
+	double* pool;
+	const uint32_t* ofirst;      // n_slots + 1 record offsets
+	const uint32_t* chunk_slot;  // chunks + 1 (chunk_slots_kernel)
+	size_t n_slots, n_local, N;
+	int K;
+	const uint64_t* slot_ids;
+	const uint32_t *nof_ptr, *nto_ptr;
+	const uint64_t *nof_id, *nto_id;
+	const int32_t* nof_slot;
+	double vel[3];
+	int has_vel;
+	double dt;
+	int32_t *src, *dest;      // per particle: source slot, destination slot (-1: leaves the lists)
+	uint32_t *stay, *mover;   // per particle flags (N + 1 entries, scanned)
+	uint32_t* part;           // per block: moved, arrived, handed over, lost
+};
+
+__global__ __launch_bounds__(kPB) void particles_locate_kernel(const MapCtx m, const DevMesh M, const PGeo G,
+                                                                  const PArgs a) {
+	__shared__ uint32_t s_off[kOffCache];
+	__shared__ uint32_t s_cnt[4];
+	uint32_t n_moved = 0, n_arrived = 0, n_handed = 0, n_lost = 0;
+	if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+	const size_t chunks = (a.N + kPB - 1) / kPB;
+	for (size_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
+		const size_t p0 = ch * kPB, p1 = p0 + kPB < a.N ? p0 + kPB : a.N;
+		__syncthreads();
+		// the slots of the pass's first and last particle bound every search
+		const size_t lo = a.chunk_slot[ch], hi = a.chunk_slot[ch + 1];
+		const size_t span = hi - lo + 2;  // offsets lo .. hi + 1
+		const bool cached = span <= size_t(kOffCache);
+		if (cached)
+			for (size_t i = threadIdx.x; i < span; i += kPB) s_off[i] = a.ofirst[lo + i];
+		__syncthreads();
+		const size_t p = p0 + threadIdx.x;
+		if (p >= p1) continue;
+		const size_t s = cached ? lo + upper_bound_idx<uint32_t>(s_off, 0, span, uint32_t(p)) - 1
+		                        : upper_bound_idx<uint32_t>(a.ofirst, lo, hi + 2, uint32_t(p)) - 1;
+		double* r = a.pool + p * size_t(a.K);
+		double x[3];
+#pragma unroll
+		for (int d = 0; d < 3; d++) {
+			const double v = a.has_vel ? a.vel[d] : r[3 + d];
+			const double step = v * a.dt;
+			const double moved = r[d] + step;
+			x[d] = real_coordinate(G, d, moved);
+			r[d] = x[d];
+		}
+		const uint64_t dst = existing_cell_at(m, M, G, x);
+		const uint64_t own = a.slot_ids[s];
+		const bool local = s < a.n_local;
+		int32_t dest = -1;
+		uint32_t stay = 0;
+		if (local) {
+			if (dst == own) {
+				dest = int32_t(s);
+				stay = 1;
+			} else {
+				bool found = false;  // not found: lost (error_cell, or not in neighbors_of)
+				if (dst != error_cell) {
+					const uint32_t e1 = a.nof_ptr[s + 1];
+					for (uint32_t e = a.nof_ptr[s]; e < e1; e++) {
+						if (a.nof_id[e] != dst) continue;
+						const int32_t ds = a.nof_slot[e];
+						found = true;
+						if (ds >= 0 && size_t(ds) < a.n_local) {
+							dest = ds;  // moved between local cells
+							n_moved++;
+						} else {
+							n_handed++;  // handed over to the owner of a known remote cell
+						}
+						break;
+					}
+				}
+				if (!found) n_lost++;
+			}
+		} else if (dst != error_cell && dst != own) {
+			// a copy of a remote neighbor: its particle arrives when the copy is
+			// in neighbors_to of a local destination
+			const int32_t ds = dm_slot(M, dst);
+			if (ds >= 0 && size_t(ds) < a.n_local) {
+				for (uint32_t e = a.nto_ptr[ds]; e < a.nto_ptr[ds + 1]; e++) {
+					if (a.nto_id[e] != own) continue;
+					dest = ds;
+					n_arrived++;
+					break;
+				}
+			}
+		}
+		a.src[p] = int32_t(s);
+		a.dest[p] = dest;
+		a.stay[p] = stay;
+		a.mover[p] = (dest >= 0 && !stay) ? 1u : 0u;
+	}
+	__syncthreads();
+	if (n_moved) atomicAdd(&s_cnt[0], n_moved);
+	if (n_arrived) atomicAdd(&s_cnt[1], n_arrived);
+	if (n_handed) atomicAdd(&s_cnt[2], n_handed);
+	if (n_lost) atomicAdd(&s_cnt[3], n_lost);
+	__syncthreads();
+	if (threadIdx.x < 4) a.part[4 * size_t(blockIdx.x) + threadIdx.x] = s_cnt[threadIdx.x];
+}
+
+__global__ void sum_parts_kernel(const uint32_t* __restrict__ part, size_t nb, uint64_t* __restrict__ out) {
+	__shared__ unsigned long long s[4];
+	if (threadIdx.x < 4) s[threadIdx.x] = 0;
+	__syncthreads();
+	unsigned long long c[4] = {0, 0, 0, 0};
+	for (size_t i = threadIdx.x; i < nb; i += blockDim.x)
+		for (int k = 0; k < 4; k++) c[k] += part[4 * i + k];
+	for (int k = 0; k < 4; k++)
+		if (c[k]) atomicAdd(&s[k], c[k]);
+	__syncthreads();
+	if (threadIdx.x < 4) out[threadIdx.x] = s[threadIdx.x];
+}
+
+__global__ void rank_by_id_kernel(const int32_t* __restrict__ order, size_t n, uint32_t* __restrict__ idrank) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x)
+		idrank[order[i]] = uint32_t(i);
+}
+
+// movers in particle order: key = destination slot << bits | rank of the
+// source cell's id, value = the particle (a stable sort keeps the index order
+// inside one source cell)
+__global__ void mover_keys_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ dest,
+                                  const uint32_t* __restrict__ mover, const uint32_t* __restrict__ mpos, size_t N,
+                                  const uint32_t* __restrict__ idrank, int bits, uint64_t* __restrict__ keys,
+                                  uint32_t* __restrict__ vals) {
+	for (size_t p = blockIdx.x * size_t(blockDim.x) + threadIdx.x; p < N; p += size_t(gridDim.x) * blockDim.x) {
+		if (!mover[p]) continue;
+		const uint32_t k = mpos[p];
+		keys[k] = (uint64_t(uint32_t(dest[p])) << bits) | idrank[src[p]];
+		vals[k] = uint32_t(p);
+	}
+}
+
+// first / one-past-last sorted mover of every destination slot
+__global__ void arrival_runs_kernel(const uint64_t* __restrict__ keys, size_t M, int bits,
+                                    uint32_t* __restrict__ arr_first, uint32_t* __restrict__ arr_end) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < M; i += size_t(gridDim.x) * blockDim.x) {
+		const uint64_t ds = keys[i] >> bits;
+		if (i == 0 || (keys[i - 1] >> bits) != ds) arr_first[ds] = uint32_t(i);
+		if (i + 1 == M || (keys[i + 1] >> bits) != ds) arr_end[ds] = uint32_t(i + 1);
+	}
+}
+
+// new record count of every slot: stayers + arrivals of a local cell, none of a remote copy
+__global__ void new_counts_kernel(const uint32_t* __restrict__ ofirst, const uint32_t* __restrict__ stayrank,
+                                  const uint32_t* __restrict__ arr_first, const uint32_t* __restrict__ arr_end,
+                                  size_t n_slots, size_t n_local, uint32_t* __restrict__ staycnt,
+                                  uint32_t* __restrict__ newcnt) {
+	for (size_t s = blockIdx.x * size_t(blockDim.x) + threadIdx.x; s < n_slots; s += size_t(gridDim.x) * blockDim.x) {
+		uint32_t st = 0, nw = 0;
+		if (s < n_local) {
+			st = stayrank[ofirst[s + 1]] - stayrank[ofirst[s]];
+			nw = st + (arr_end[s] - arr_first[s]);
+		}
+		staycnt[s] = st;
+		newcnt[s] = nw;
+	}
+}
+
+__global__ void byte_offsets_kernel(const uint32_t* __restrict__ nfirst, size_t n, uint64_t rec,
+                                    uint64_t* __restrict__ noff) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x)
+		noff[i] = uint64_t(nfirst[i]) * rec;
+}
+
+__device__ __forceinline__ void copy_record(double* __restrict__ dst, const double* __restrict__ src, int K) {
+	for (int k = 0; k < K; k++) dst[k] = src[k];
+}
+
+__global__ void scatter_stayers_kernel(const double* __restrict__ pool, double* __restrict__ out, int K, size_t N,
+                                       const int32_t* __restrict__ src, const uint32_t* __restrict__ stay,
+                                       const uint32_t* __restrict__ stayrank, const uint32_t* __restrict__ ofirst,
+                                       const uint32_t* __restrict__ nfirst) {
+	for (size_t p = blockIdx.x * size_t(blockDim.x) + threadIdx.x; p < N; p += size_t(gridDim.x) * blockDim.x) {
+		if (!stay[p]) continue;
+		const int32_t s = src[p];
+		const size_t q = size_t(nfirst[s]) + (stayrank[p] - stayrank[ofirst[s]]);
+		copy_record(out + q * size_t(K), pool + p * size_t(K), K);
+	}
+}
+
+__global__ void scatter_movers_kernel(const double* __restrict__ pool, double* __restrict__ out, int K, size_t M,
+                                      const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int bits,
+                                      const uint32_t* __restrict__ nfirst, const uint32_t* __restrict__ staycnt,
+                                      const uint32_t* __restrict__ arr_first) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < M; i += size_t(gridDim.x) * blockDim.x) {
+		const uint64_t ds = keys[i] >> bits;
+		const size_t q = size_t(nfirst[ds]) + staycnt[ds] + (uint32_t(i) - arr_first[ds]);
+		copy_record(out + q * size_t(K), pool + size_t(vals[i]) * size_t(K), K);
+	}
+}
+
+int bits_for(size_t n) {  // every value < n fits in this many bits (at least 1)
+	int b = 1;
+	while (b < 63 && (size_t(1) << b) < n) b++;
+	return b;
+}
+
+void require_cartesian(const Grid& g) {
+	DX_REQUIRE(g.initialized, "not initialized");
+	DX_REQUIRE(g.geo_block.empty(), "the grid holds a stretched geometry block (Cartesian geometry only)");
+}
+
+}  // namespace
+
+void existing_cells_at(Grid& g, const double* xyz, size_t n, uint64_t* ids) {
+	require_cartesian(g);
+	if (!n) return;
+	DX_REQUIRE(xyz && ids, "null pointer");
+	hipStream_t s = g.s_comp;
+	DBuf<double> dx;
+	DBuf<uint64_t> di;
+	dx.alloc(3 * n);
+	di.alloc(n);
+	h2d(dx.p, xyz, 3 * n * sizeof(double), s);
+	cells_at_kernel<<<grid_for(n, 256), 256, 0, s>>>(g.m, g.dm(), make_geo(g), dx.p, n, di.p);
+	HIP_CHECK(hipGetLastError());
+	d2h_small(ids, di.p, n * sizeof(uint64_t), s);
+}
+
+void particles_step(Grid& g, int fid, int K, const double* velocity, double dt, uint64_t stats[5]) {
+	require_cartesian(g);
+	Field& f = field(g, fid);
+	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	DX_REQUIRE(K >= 3, "a particle record has at least 3 doubles (the position)");
+	DX_REQUIRE(velocity || K >= 6, "per-particle velocities (velocity == NULL) need records of at least 6 doubles");
+	DX_REQUIRE(stats, "null pointer");
+	for (int k = 0; k < 5; k++) stats[k] = 0;
+	hipStream_t s = g.s_comp;
+	const size_t ns = g.n_slots, nl = g.n_local;
+	if (!ns || !f.voff.p) return;
+	const uint64_t rec = uint64_t(K) * sizeof(double);
+
+	// record offsets of the slots; every cell a whole number of records
+	DBuf<uint32_t> ofirst;
+	DBuf<int32_t> flag;
+	ofirst.alloc(ns + 1);
+	flag.alloc(1);
+	HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, s));
+	const uint64_t total = var_total(f, ns, s);
+	DX_REQUIRE(total / rec < (uint64_t(1) << 31), "more than 2^31 particles on one process");
+	record_offsets_kernel<<<grid_for(ns + 1, 256), 256, 0, s>>>(f.voff.p, ns + 1, rec, ofirst.p, flag.p);
+	HIP_CHECK(hipGetLastError());
+	int32_t bad = 0;
+	d2h_small(&bad, flag.p, 4, s);
+	DX_REQUIRE(!bad, "a cell's payload is not a multiple of 8 * record_doubles bytes");
+	const size_t N = size_t(total / rec);
+	if (!N) return;
+	ensure_csr(g);
+
+	// 1. locate
+	DBuf<int32_t> src, dest;
+	DBuf<uint32_t> stay, mover, stayrank, mpos, part;
+	src.alloc(N);
+	dest.alloc(N);
+	stay.alloc(N + 1);
+	mover.alloc(N + 1);
+	stayrank.alloc(N + 1);
+	mpos.alloc(N + 1);
+	const unsigned nb = grid_for(N, kPB, 8192);
+	part.alloc(4 * size_t(nb));
+	const size_t chunks = (N + kPB - 1) / kPB;
+	DBuf<uint32_t> chunk_slot;
+	chunk_slot.alloc(chunks + 1);
+	chunk_slots_kernel<<<grid_for(chunks + 1, 256), 256, 0, s>>>(ofirst.p, ns, N, chunks, chunk_slot.p);
+	HIP_CHECK(hipGetLastError());
+	PArgs a{};
+	a.pool = reinterpret_cast<double*>(f.data.p);
+	a.ofirst = ofirst.p;
+	a.chunk_slot = chunk_slot.p;
+	a.n_slots = ns;
+	a.n_local = nl;
+	a.N = N;
+	a.K = K;
+	a.slot_ids = g.slot_ids.p;
+	a.nof_ptr = g.nof_ptr.p;
+	a.nto_ptr = g.nto_ptr.p;
+	a.nof_id = g.nof_id.p;
+	a.nto_id = g.nto_id.p;
+	a.nof_slot = g.nof_slot.p;
+	a.has_vel = velocity ? 1 : 0;
+	for (int d = 0; d < 3; d++) a.vel[d] = velocity ? velocity[d] : 0.0;
+	a.dt = dt;
+	a.src = src.p;
+	a.dest = dest.p;
+	a.stay = stay.p;
+	a.mover = mover.p;
+	a.part = part.p;
+	particles_locate_kernel<<<nb, kPB, 0, s>>>(g.m, g.dm(), make_geo(g), a);
+	HIP_CHECK(hipGetLastError());
+	DBuf<uint64_t> dstats;
+	dstats.alloc(4);
+	sum_parts_kernel<<<1, 256, 0, s>>>(part.p, nb, dstats.p);
+	HIP_CHECK(hipGetLastError());
+
+	// 2. ranks of the stayers and of the movers
+	size_t n_stay = 0, M = 0;
+	scan_exclusive_u32_pair(stay.p, stayrank.p, mover.p, mpos.p, N, s, n_stay, M);
+
+	// 3. movers sorted by (destination slot, source id), index order kept
+	DBuf<uint32_t> arr_first, arr_end;
+	arr_first.alloc(nl + 1);
+	arr_end.alloc(nl + 1);
+	HIP_CHECK(hipMemsetAsync(arr_first.p, 0, (nl + 1) * 4, s));
+	HIP_CHECK(hipMemsetAsync(arr_end.p, 0, (nl + 1) * 4, s));
+	DBuf<uint64_t> keys, keys2;
+	DBuf<uint32_t> vals, vals2;
+	const int bits = bits_for(ns);
+	if (M) {
+		// rank of every slot's id among the slots' ids
+		DBuf<int32_t> iota, order;
+		DBuf<uint64_t> sorted_ids;
+		DBuf<uint32_t> idrank;
+		DBuf<uint8_t> temp;
+		iota.alloc(ns);
+		order.alloc(ns);
+		sorted_ids.alloc(ns);
+		idrank.alloc(ns);
+		k_iota_i32(iota.p, ns, 0, s);
+		size_t tb = 0;
+		HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, g.slot_ids.p, sorted_ids.p, iota.p, order.p, ns, 0,
+		                                             map_id_bits(g.m), s));
+		temp.alloc(tb + 1);
+		HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, g.slot_ids.p, sorted_ids.p, iota.p, order.p, ns, 0,
+		                                             map_id_bits(g.m), s));
+		rank_by_id_kernel<<<grid_for(ns, 256), 256, 0, s>>>(order.p, ns, idrank.p);
+		HIP_CHECK(hipGetLastError());
+		keys.alloc(M);
+		keys2.alloc(M);
+		vals.alloc(M);
+		vals2.alloc(M);
+		mover_keys_kernel<<<grid_for(N, 256), 256, 0, s>>>(src.p, dest.p, mover.p, mpos.p, N, idrank.p, bits, keys.p,
+		                                                   vals.p);
+		HIP_CHECK(hipGetLastError());
+		const int end_bit = bits + bits_for(nl);
+		tb = 0;
+		HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, keys2.p, vals.p, vals2.p, M, 0, end_bit, s));
+		temp.alloc(tb + 1);
+		HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys.p, keys2.p, vals.p, vals2.p, M, 0, end_bit, s));
+		// 4. arrivals per destination
+		arrival_runs_kernel<<<grid_for(M, 256), 256, 0, s>>>(keys2.p, M, bits, arr_first.p, arr_end.p);
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(hipStreamSynchronize(s));  // temp and the unsorted lists go out of scope
+	}
+
+	// 5. new sizes
+	DBuf<uint32_t> staycnt, newcnt, nfirst;
+	staycnt.alloc(ns + 1);
+	newcnt.alloc(ns + 1);
+	nfirst.alloc(ns + 1);
+	new_counts_kernel<<<grid_for(ns, 256), 256, 0, s>>>(ofirst.p, stayrank.p, arr_first.p, arr_end.p, ns, nl, staycnt.p,
+	                                                    newcnt.p);
+	HIP_CHECK(hipGetLastError());
+	const size_t Nn = scan_exclusive_u32(newcnt.p, nfirst.p, ns, s);
+	DX_REQUIRE(Nn == n_stay + M, "particle counts do not add up");
+	DBuf<uint64_t> noff;
+	noff.alloc(ns + 1);
+	byte_offsets_kernel<<<grid_for(ns + 1, 256), 256, 0, s>>>(nfirst.p, ns + 1, rec, noff.p);
+	HIP_CHECK(hipGetLastError());
+
+	// 6. scatter into a fresh pool
+	DBuf<uint8_t> nd;
+	nd.alloc(size_t(Nn) * rec + 1);
+	double* out = reinterpret_cast<double*>(nd.p);
+	if (n_stay) {
+		scatter_stayers_kernel<<<grid_for(N, 256), 256, 0, s>>>(a.pool, out, K, N, src.p, stay.p, stayrank.p, ofirst.p,
+		                                                        nfirst.p);
+		HIP_CHECK(hipGetLastError());
+	}
+	if (M) {
+		scatter_movers_kernel<<<grid_for(M, 256), 256, 0, s>>>(a.pool, out, K, M, keys2.p, vals2.p, bits, nfirst.p,
+		                                                       staycnt.p, arr_first.p);
+		HIP_CHECK(hipGetLastError());
+	}
+	uint64_t h[4] = {0, 0, 0, 0};
+	d2h_small(h, dstats.p, sizeof(h), s);  // drains s
+	f.data.swap(nd);
+	f.voff.swap(noff);
+	field_written(f);
+	stats[0] = n_stay;
+	for (int k = 0; k < 4; k++) stats[1 + k] = h[k];
+}
+
+}  // namespace dccrgx

@@ -828,6 +828,28 @@ class Dccrg:
         a = np.ascontiguousarray(data, np.uint8)
         check(lib().dccrgx_halo_place(self.h, int(hood), int(peer), _ptr(a), a.size))
 
+    # ---- particles in cells (tests/particles/simple.cpp) -----------------------------
+    def get_existing_cells_at(self, points):
+        """get_existing_cell(coordinate) (dccrg.hpp:6316) for (n, 3) points:
+        the smallest leaf this process knows at each, 0 (error_cell) else."""
+        p = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+        out = np.zeros(p.shape[0], np.uint64)
+        check(lib().dccrgx_get_existing_cells_at(self.h, _ptr(p), p.shape[0], _ptr(out)))
+        return out
+
+    def particles_step(self, field, record_doubles=3, velocity=None, dt=1.0, halo=False):
+        """One step of propagate_particles (simple.cpp:52-97) on the variable
+        float64 field `field` of `record_doubles` doubles per particle (0..2
+        the position; velocity None: doubles 3..5 each particle's velocity).
+        halo=True refreshes the copies of remote neighbors first.  Returns
+        the step's counts."""
+        if halo:
+            self.update_copies_of_remote_neighbors()
+        v = None if velocity is None else (C.c_double * 3)(*[float(x) for x in velocity])
+        st = (C.c_uint64 * 5)()
+        check(lib().dccrgx_particles_step(self.h, field.id, int(record_doubles), v, float(dt), st))
+        return dict(zip(("stayed", "moved", "arrived", "handed_over", "lost"), (int(x) for x in st)))
+
     # ---- built-in sweeps ------------------------------------------------------------
     def gol_step(self, state: Field, region="all"):
         check(lib().dccrgx_gol_step(self.h, state.id, REGION[region]))

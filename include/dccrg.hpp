@@ -42,6 +42,7 @@
 #include <algorithm>
 #include <array>
 #include <climits>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -382,6 +383,55 @@ public:
 		const auto c = get_center(cell), L = get_length(cell);
 		return {{c[0] + L[0] / 2, c[1] + L[1] / 2, c[2] + L[2] / 2}};
 	}
+	// dccrg_cartesian_geometry.hpp:242-264
+	std::array<double, 3> get_end() const {
+		const std::array<uint64_t, 3> len = length_ ? length_->get() : std::array<uint64_t, 3>{{1, 1, 1}};
+		std::array<double, 3> r;
+		for (size_t d = 0; d < 3; d++) r[d] = p_.start[d] + double(len[d]) * p_.level_0_cell_length[d];
+		return r;
+	}
+	// get_real_coordinate (521-565): the coordinate itself inside the grid, its
+	// periodic image in a periodic dimension, a quiet NaN outside otherwise
+	std::array<double, 3> get_real_coordinate(const std::array<double, 3>& given) const {
+		const std::array<double, 3> start = get_start(), end = get_end();
+		const double nan = std::numeric_limits<double>::quiet_NaN();
+		std::array<double, 3> r{{nan, nan, nan}};
+		for (size_t d = 0; d < 3; d++) {
+			if (given[d] >= start[d] && given[d] <= end[d]) {
+				r[d] = given[d];
+			} else if (topology_ && topology_->is_periodic(d)) {
+				const double grid_length = end[d] - start[d];
+				if (given[d] < start[d]) {
+					const double distance = start[d] - given[d];
+					r[d] = given[d] + grid_length * std::ceil(distance / grid_length);
+				} else {
+					const double distance = given[d] - end[d];
+					r[d] = given[d] - grid_length * std::ceil(distance / grid_length);
+				}
+			}
+		}
+		return r;
+	}
+	// get_indices(coordinate) (574-607): in units of the finest cells,
+	// error_index outside a non-periodic dimension
+	std::array<uint64_t, 3> get_indices(const std::array<double, 3>& given) const {
+		std::array<uint64_t, 3> r{{error_index, error_index, error_index}};
+		const std::array<double, 3> start = get_start(), end = get_end(), c = get_real_coordinate(given);
+		int R = 0;
+		if (g_) dccrgx_get_maximum_refinement_level(g_, &R);
+		for (size_t d = 0; d < 3; d++)
+			if (c[d] >= start[d] && c[d] <= end[d])
+				r[d] = uint64_t(std::floor((c[d] - start[d]) / (p_.level_0_cell_length[d] / double(uint64_t(1) << R))));
+		return r;
+	}
+	// get_cell(level, coordinate) (495-507)
+	uint64_t get_cell(const int refinement_level, const std::array<double, 3>& coordinate) const {
+		int R = 0;
+		if (g_) dccrgx_get_maximum_refinement_level(g_, &R);
+		if (!g_ || refinement_level < 0 || refinement_level > R) return error_cell;
+		const std::array<uint64_t, 3> ind = get_indices(coordinate);
+		return dccrgx_get_cell_from_indices(g_, ind.data(), refinement_level);
+	}
 
 private:
 	Parameters p_;
@@ -426,6 +476,55 @@ public:
 		std::vector<T> v(n);
 		if (n) download(v.data(), n, slot0);
 		return v;
+	}
+
+private:
+	dccrgx_grid* g_ = nullptr;
+	int id_ = -1;
+};
+
+// A device-resident variable-size field (a Cell_Data with a std::vector member,
+// e.g. the particle lists of tests/particles/cell.hpp): every slot owns a
+// run of T in one device pool.  Upload and download move a range of slots.
+template <class T>
+class Device_Variable_Field {
+public:
+	Device_Variable_Field() = default;
+	Device_Variable_Field(dccrgx_grid* g, int id) : g_(g), id_(id) {}
+	int id() const { return id_; }
+	operator int() const { return id_; }
+	// element counts of slots [slot0, slot0 + n)
+	std::vector<uint64_t> sizes(size_t n, size_t slot0 = 0) const {
+		std::vector<uint64_t> b(n);
+		detail::check(dccrgx_variable_field_sizes(g_, id_, slot0, n, b.data()));
+		for (auto& v : b) v /= sizeof(T);
+		return b;
+	}
+	// slots [slot0, slot0 + cells.size()) take the given values (and sizes)
+	void upload(const std::vector<std::vector<T>>& cells, size_t slot0 = 0) const {
+		std::vector<uint64_t> b(cells.size());
+		std::vector<T> flat;
+		for (size_t i = 0; i < cells.size(); i++) {
+			b[i] = cells[i].size() * sizeof(T);
+			flat.insert(flat.end(), cells[i].begin(), cells[i].end());
+		}
+		detail::check(dccrgx_variable_field_resize(g_, id_, slot0, b.size(), b.data()));
+		detail::check(dccrgx_variable_field_upload(g_, id_, slot0, b.size(), flat.data(), flat.size() * sizeof(T)));
+	}
+	std::vector<std::vector<T>> download(size_t n, size_t slot0 = 0) const {
+		const std::vector<uint64_t> cnt = sizes(n, slot0);
+		size_t total = 0;
+		for (const uint64_t c : cnt) total += size_t(c);
+		std::vector<T> flat(total);
+		size_t got = 0;
+		detail::check(dccrgx_variable_field_download(g_, id_, slot0, n, flat.data(), total * sizeof(T), &got));
+		std::vector<std::vector<T>> cells(n);
+		size_t o = 0;
+		for (size_t i = 0; i < n; i++) {
+			cells[i].assign(flat.begin() + long(o), flat.begin() + long(o + cnt[i]));
+			o += size_t(cnt[i]);
+		}
+		return cells;
 	}
 
 private:
@@ -623,6 +722,13 @@ public:
 		return nullptr;
 	}
 	std::array<double, 3> get_center(const uint64_t cell) const { return geometry_rw.get_center(cell); }  // 771
+	// the smallest leaf this process knows at the coordinate, error_cell
+	// outside the grid or where nothing is known (6316-6336)
+	uint64_t get_existing_cell(const std::array<double, 3>& coordinate) const {
+		uint64_t id = error_cell;
+		detail::check(dccrgx_get_existing_cells_at(g_, coordinate.data(), 1, &id));
+		return id;
+	}
 
 	// get_neighbors_of / _to (819 / 883): nullptr for a cell that is not local
 	// or a neighborhood that does not exist; valid until the next structural change
@@ -1059,6 +1165,12 @@ public:
 		detail::check(dccrgx_add_field(g_, name.c_str(), sizeof(T), transfer ? 1 : 0, &id));
 		return Device_Field<T>(g_, id);
 	}
+	template <class T>
+	Device_Variable_Field<T> add_variable_field(const std::string& name, bool transfer) {
+		int id = -1;
+		detail::check(dccrgx_add_variable_field(g_, name.c_str(), transfer ? 1 : 0, &id));
+		return Device_Variable_Field<T>(g_, id);
+	}
 	int payload_field() const { return payload_; }
 	// host Cell_Data <-> device payload field
 	void upload() { upload_all(); }
@@ -1082,6 +1194,19 @@ public:
 	// list: 8 x uint64 per cell (Cell_Data::data[1..8])
 	void get_live_neighbors(const Device_Field<uint32_t>& state, const Device_Field<std::array<uint64_t, 8>>& list) {
 		detail::check(dccrgx_get_live_neighbors(g_, state.id(), list.id()));
+	}
+
+	// particles in cells (tests/particles/simple.cpp:52-97): one step of
+	// propagate_particles over the local cells and the copies of remote
+	// neighbors.  Records of K doubles, 0..2 the position; velocity nullptr
+	// (K >= 6): doubles 3..5 of each record.  Returns {stayed, moved between
+	// local cells, arrived from remote copies, handed over, lost}.
+	std::array<uint64_t, 5> particles_step(const Device_Variable_Field<double>& particles, const int record_doubles,
+	                                       const std::array<double, 3>* velocity, const double dt) {
+		std::array<uint64_t, 5> st{{0, 0, 0, 0, 0}};
+		detail::check(dccrgx_particles_step(g_, particles.id(), record_doubles, velocity ? velocity->data() : nullptr, dt,
+		                                    st.data()));
+		return st;
 	}
 
 	// advection (tests/advection): fields density, vx, vy, vz, lx, ly, lz

@@ -389,6 +389,33 @@ int dccrgx_variable_field_device_ptr(dccrgx_grid* g, int field_id, void** data, 
  * (one per removed cell, may be NULL) and concatenated bytes */
 int dccrgx_removed_variable_field_download(dccrgx_grid* g, int field_id, uint64_t* sizes, void* bytes, size_t cap,
                                            size_t* nbytes);
+/* ---- particles in cells (tests/particles/simple.cpp) -----------------------
+ * get_existing_cell(coordinate) (dccrg.hpp:6316-6336) for n host coordinates
+ * (x, y, z each): the smallest leaf known to this process at each one, 0
+ * (error_cell) outside the grid or where nothing is known.  The wrap and the
+ * indices are Cartesian_Geometry::get_real_coordinate / get_indices
+ * (dccrg_cartesian_geometry.hpp:521-607): a coordinate exactly at the grid's
+ * end indexes one past the last cell and yields 0, in a periodic dimension
+ * too.  Cartesian geometry only (DCCRGX_EINVAL with a stretched block). */
+int dccrgx_get_existing_cells_at(dccrgx_grid* g, const double* xyz, size_t n, uint64_t* ids);
+/* One step of propagate_particles (simple.cpp:52-97) on the device.  The
+ * variable field holds fp64 records of record_doubles (K >= 3) doubles per
+ * particle, doubles 0..2 the position, the rest carried along; velocity NULL
+ * (K >= 6) takes each particle's velocity from doubles 3..5.  Over the local
+ * cells and the copies of remote neighbors: x' = real_coordinate(x + v dt)
+ * (product and sum rounded separately) is stored back; a particle whose leaf
+ * is its cell stays, one whose leaf is a local cell in neighbors_of of its
+ * cell (for a remote copy: a local cell with the copy in neighbors_to) is
+ * appended there, any other leaves this process's lists.  A local cell ends
+ * with its stayers in their previous order, then the arrivals ordered by
+ * (source cell id, index in the source cell); remote copies end empty.
+ * stats = {stayed, moved between local cells, arrived from remote copies,
+ * handed over (a known remote cell in neighbors_of), lost}.  DCCRGX_EINVAL:
+ * a fixed-size field, a cell whose bytes are no multiple of 8 K, K < 3,
+ * velocity NULL with K < 6, a stretched geometry block. */
+int dccrgx_particles_step(dccrgx_grid* g, int var_field, int record_doubles, const double* velocity, double dt,
+                          uint64_t* stats);
+
 /* set_send_single_cells 6677 / get_send_single_cells 6684: one message per
  * cell (tag = position + 1) instead of one per process.  On, the remote
  * neighbor updates put each cell's fixed-size payload on the wire as its own
