@@ -152,6 +152,7 @@ _SIGS = {
     "dccrgx_advection_adapt": (C.c_int, [vp, vp, vp]),
     "dccrgx_advection_refine_candidates": (C.c_int, [vp, C.c_int, C.c_double, C.c_double, vp, sz, P(sz)]),
     "dccrgx_advection_layout": (C.c_int, [vp, P(u64)]),
+    "dccrgx_advection_occupancy": (C.c_int, [vp, P(u64)]),
     "dccrgx_advection_length_source": (C.c_int, [vp, P(C.c_int), P(C.c_int)]),
     "dccrgx_poisson_cache": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, sz]),
     "dccrgx_poisson_solve": (C.c_int, [vp, C.c_uint, C.c_uint, C.c_double, C.c_double, C.c_double, C.c_int,

@@ -2739,6 +2739,28 @@ int dccrgx_advection_layout(dccrgx_grid* gp, uint64_t out[12]) {
 	});
 }
 
+int dccrgx_advection_occupancy(dccrgx_grid* gp, uint64_t out[6]) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		DX_REQUIRE(out, "null output");
+		ensure_tiles(g);
+		// the launch of the fields last passed to an advection call (before
+		// the first sweep: the one it will make)
+		const bool valid = g.adv_fids_valid;
+		const bool rec = valid && ensure_nbrec(g, g.adv_fids) != nullptr;
+		const bool len = valid && ensure_len_table(g, g.adv_fids, false) != nullptr;
+		for (int kind = 0; kind < 2; kind++) {
+			const Grid::SweepLaunch& L = adv_sweep_launch(g, kind, rec, len);
+			int k = 0;
+			HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, L.fn, 512, L.lds));
+			out[3 * kind] = uint64_t(L.blocks_per_cu);
+			out[3 * kind + 1] = uint64_t(k);
+			out[3 * kind + 2] = L.lds;
+		}
+		return 0;
+	});
+}
+
 int dccrgx_advection_length_source(dccrgx_grid* gp, const int fids[7], int* out) {
 	return guard([&] {
 		GRID_OR_FAIL(gp);

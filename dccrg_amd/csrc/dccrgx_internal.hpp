@@ -749,6 +749,15 @@ struct Grid {
 	// reports the bytes of the sweep of these fields)
 	int adv_fids[7] = {-1, -1, -1, -1, -1, -1, -1};
 	bool adv_fids_valid = false;
+	// how k_advection_tiles launches its two persistent kernels (0 the regular
+	// tiles', 1 the other tiles'): the kernel, the dynamic LDS asked for and
+	// launched with, and the blocks per CU the runtime reports for that launch
+	// (adv_sweep_launch; cached on the kernel and the LDS size)
+	struct SweepLaunch {
+		const void* fn = nullptr;
+		size_t lds_min = 0, lds = 0;
+		int blocks_per_cu = 0;
+	} adv_launch[2];
 	std::vector<int> halo_fields;  // fixed-size fields of the halo in flight (written again when it lands)
 	std::map<int, UserHood> uhoods;  // add_neighborhood ids
 	GolAmrTables gola;  // refined game of life: per-mesh tables (gol_amr.hip)
@@ -1051,6 +1060,29 @@ void k_tile_levels(const uint8_t* slot_lvl, const uint32_t* ext_pk, size_t n_ext
 #ifndef DCCRGX_LEN_OWN
 #define DCCRGX_LEN_OWN 1
 #endif
+// 1: the length-table kernel of the regular tiles (DCCRGX_LEN_LDS) / of the
+// other tiles (DCCRGX_LEN_LDS_GEN) carries the lengths through LDS rows as
+// the field-reading kernels do: the layout before the lengths stayed in
+// registers / a level byte per column, kept for paired A/Bs
+#ifndef DCCRGX_LEN_LDS
+#define DCCRGX_LEN_LDS 0
+#endif
+#ifndef DCCRGX_LEN_LDS_GEN
+#define DCCRGX_LEN_LDS_GEN DCCRGX_LEN_LDS
+#endif
+// blocks per CU the length-table kernels are compiled for (2 x that many
+// waves per SIMD) and at most launched with; the launch takes the number
+// the runtime reports (adv_sweep_launch)
+#ifndef DCCRGX_REG_BLOCKS
+#define DCCRGX_REG_BLOCKS ((DCCRGX_LEN_OWN && !DCCRGX_LEN_LDS) ? 3 : 2)
+#endif
+#ifndef DCCRGX_GEN_BLOCKS
+#define DCCRGX_GEN_BLOCKS ((DCCRGX_LEN_OWN && !DCCRGX_LEN_LDS_GEN) ? 3 : 2)
+#endif
+// the launch k_advection_tiles makes (or would make, given whether the
+// neighbor records / the length table are in use) for the regular (kind 0)
+// or the other tiles (kind 1): fills and returns g.adv_launch[kind]
+const Grid::SweepLaunch& adv_sweep_launch(Grid& g, int kind, bool nbrec, bool lentab);
 // the neighbor records for the sweep of fields fids (rho vx vy vz lx ly lz),
 // rebuilt when stale; nullptr when a velocity / length field is external
 // (or DCCRGX_NBREC=0): the sweeps then read the fields

@@ -712,10 +712,16 @@ __device__ __forceinline__ uint32_t nb_one_row(uint32_t a) { return a == 2 ? 5u 
 // A regular tile and its neighbor boxes are one level, the record's last
 // word, so the tile's three lengths are block-uniform values from the table:
 // the out-of-tile rows shrink from 30 to 12 (per side the density and the
-// velocity along the side's axis), the side columns' length rows are staged
-// from the table, and (DCCRGX_LEN_OWN) so are the own cells', which leaves
-// four own loads of seven.  The flux expressions read the same LDS rows with
-// the same bits, so the densities are bitwise the field-reading kernel's.
+// velocity along the side's axis) and (DCCRGX_LEN_OWN) the own loads from
+// seven to four.  The lengths never enter LDS (LREG): shd keeps the four rows
+// rho, vx, vy, vz, and every length a face reads - the own cell's, the +a
+// neighbor's, the -a boundary faces' - is the tile's uniform tl[], the same
+// bits in the same operands, so the densities are bitwise the field-reading
+// kernel's.  That is a third fewer LDS instructions per tile and 42.3 KB of
+// LDS instead of 64 KB; at 76 VGPRs the kernel is compiled for, and
+// launched with, three blocks per CU (DCCRGX_REG_BLOCKS;
+// profiles/len_lds_ab.md).  DCCRGX_LEN_LDS=1 or DCCRGX_LEN_OWN=0 keep the
+// seven rows, staged from the table, and two blocks.
 template <int MINW, bool REC, bool LEN>
 __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs P, double* __restrict__ rho_out,
                                                                          const RegTileMeta* __restrict__ meta,
@@ -725,12 +731,15 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 #pragma clang fp contract(off)
 	static_assert(!(REC && LEN), "the length table is for the default kernels only");
 	constexpr bool LOWN = LEN && DCCRGX_LEN_OWN;
+	constexpr bool LREG = LOWN && !DCCRGX_LEN_LDS;  // the lengths stay in registers
 	// rows rho, vx, vy, vz, lx, ly, lz; columns 0..511 the tile's own cells,
 	// 512 + 64 d + (face cell) the out-of-tile neighbor across side d (only
 	// rows rho, lx, ly, lz and the velocity along d's axis are filled), so
-	// every face reads its neighbor through one LDS index, whichever side
+	// every face reads its neighbor through one LDS index, whichever side.
+	// LREG: no length rows, every length a face reads is the tile's tl[]
 	constexpr uint32_t W = 512 + 6 * 64;
-	__shared__ double shd[7][W];
+	constexpr int NROW = LREG ? 4 : 7;
+	__shared__ double shd[NROW][W];
 	__shared__ double shg[3][512];  // flux through each cell's +x, +y, +z face
 	__shared__ double shm[3][64];   // flux through the tile's -x, -y, -z boundary faces
 	__shared__ double lt[LEN ? 96 : 1];  // LEN: the per-level lengths
@@ -812,15 +821,23 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 			}
 		}
 	};
-	// a loaded tile into LDS (after the barrier that ends the previous tile's reads)
-	auto stage = [&](const RegSet& r, const RM& ms) {
-		double tl[3] = {0, 0, 0};  // LEN: the tile's lengths, block-uniform
+	// LEN: a tile's lengths, block-uniform (lt: after the first barrier)
+	struct TL {
+		double v[3];
+	};
+	auto lengths = [&](const RM& m) {
+		TL tl{{0, 0, 0}};
 		if (LEN) {
-			const uint32_t lv = 3u * ms.lvl();
-			tl[0] = lt[lv]; tl[1] = lt[lv + 1]; tl[2] = lt[lv + 2];
+			const uint32_t lv = 3u * m.lvl();
+			tl.v[0] = lt[lv]; tl.v[1] = lt[lv + 1]; tl.v[2] = lt[lv + 2];
 		}
+		return tl;
+	};
+	// a loaded tile into LDS (after the barrier that ends the previous tile's reads)
+	auto stage = [&](const RegSet& r, const TL& tlv) {
+		const double (&tl)[3] = tlv.v;
 #pragma unroll
-		for (int k = 0; k < 7; k++) shd[k][tid] = LOWN && k >= 4 ? tl[k - 4] : r.c[k];
+		for (int k = 0; k < NROW; k++) shd[k][tid] = LOWN && k >= 4 ? tl[k - 4] : r.c[k];
 #pragma unroll
 		for (int i = 0; i < 4; i++) {
 			const uint32_t row = w + 8u * uint32_t(i);
@@ -831,26 +848,32 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 						shd[1u + (d >> 1)][col] = r.e[i];
 					} else {
 						shd[0][col] = r.e[i];
-						shd[4][col] = tl[0]; shd[5][col] = tl[1]; shd[6][col] = tl[2];
+						if (!LREG) {
+							shd[4 % NROW][col] = tl[0]; shd[5 % NROW][col] = tl[1]; shd[6 % NROW][col] = tl[2];
+						}
 					}
 				}
 			} else if (REC) {
 				if (row < 24u) {
 					const uint32_t d = row >> 2, val = row & 3u, a = d >> 1, col = 512u + 64u * d + lane;
 					const uint32_t k = val == 0 ? 0u : (val == 1 ? 4u + a : (val == 2 ? nb_area_row(a) : 1u + a));
-					shd[k][col] = r.e[i];
-					if (val == 2) shd[nb_one_row(a)][col] = 1.0;
+					shd[k % NROW][col] = r.e[i];
+					if (val == 2) shd[nb_one_row(a) % NROW][col] = 1.0;
 				}
 			} else if (row < 30u) {
 				const uint32_t d = row / 5u, val = row - 5u * d;
-				shd[vrow(val, d >> 1)][512u + 64u * d + lane] = r.e[i];
+				shd[vrow(val, d >> 1) % NROW][512u + 64u * d + lane] = r.e[i];
 			}
 		}
 	};
+	// column i of LDS row k (LREG: a length row is the tile's length)
+	auto lrow = [&](const TL& tl, int k, uint32_t i) -> double {
+		return LREG && k >= 4 ? tl.v[k - 4] : shd[k % NROW][i];
+	};
 	// the staged tile tc from LDS
-	auto compute = [&](const RM& mc) {
+	auto compute = [&](const RM& mc, const TL& tl) {
 		const uint32_t ts = mc.ts;
-		const double cd = shd[0][tid], clx = shd[4][tid], cly = shd[5][tid], clz = shd[6][tid];
+		const double cd = shd[0][tid], clx = lrow(tl, 4, tid), cly = lrow(tl, 5, tid), clz = lrow(tl, 6, tid);
 		const double cva[3] = {shd[1][tid], shd[2][tid], shd[3][tid]};
 		// pass 1: the +x, +y, +z face of every cell, once per face, branch-free
 		// (a missing face beyond a non-periodic boundary evaluates zeros and
@@ -859,7 +882,7 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 		for (int a = 0; a < 3; a++) {
 			const uint32_t li = lp[a];
 			const double g = adv_face_g(a, cd, clx, cly, clz, cva[a],
-			                            AdvNb{shd[0][li], shd[4][li], shd[5][li], shd[6][li], shd[1 + a][li]}, dt);
+			                            AdvNb{shd[0][li], lrow(tl, 4, li), lrow(tl, 5, li), lrow(tl, 6, li), shd[1 + a][li]}, dt);
 			const bool has = l[a] < 7 || mc.nst(2 * a + 1) >= 0;
 			shg[a][tid] = has ? g : 0.0;
 		}
@@ -867,11 +890,12 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 		// waves 0..2, wave-uniform
 		if (w < 3 && mc.nst(2 * w) >= 0) {
 			const uint32_t k = 512u + 64u * (2u * w) + lane;
-			const AdvNb self{shd[0][bcell], shd[4][bcell], shd[5][bcell], shd[6][bcell], shd[1 + w][bcell]};
+			const AdvNb self{shd[0][bcell], lrow(tl, 4, bcell), lrow(tl, 5, bcell), lrow(tl, 6, bcell), shd[1 + w][bcell]};
+			const double kx = lrow(tl, 4, k), ky = lrow(tl, 5, k), kz = lrow(tl, 6, k);
 			double gmv;
-			if (w == 0) gmv = adv_face_g(0, shd[0][k], shd[4][k], shd[5][k], shd[6][k], shd[1][k], self, dt);
-			else if (w == 1) gmv = adv_face_g(1, shd[0][k], shd[4][k], shd[5][k], shd[6][k], shd[2][k], self, dt);
-			else gmv = adv_face_g(2, shd[0][k], shd[4][k], shd[5][k], shd[6][k], shd[3][k], self, dt);
+			if (w == 0) gmv = adv_face_g(0, shd[0][k], kx, ky, kz, shd[1][k], self, dt);
+			else if (w == 1) gmv = adv_face_g(1, shd[0][k], kx, ky, kz, shd[2][k], self, dt);
+			else gmv = adv_face_g(2, shd[0][k], kx, ky, kz, shd[3][k], self, dt);
 			shm[w][lane] = gmv;
 		}
 		__syncthreads();
@@ -913,7 +937,8 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 	// tile tL, then computed; tS becomes the refilled tile (t1: none)
 	auto body = [&](RegSet& S, RM& mS, uint32_t& tS) {
 		__syncthreads();  // the previous tile's faces have been read from LDS
-		stage(S, mS);
+		const TL tl = lengths(mS);
+		stage(S, tl);
 		__syncthreads();
 		const RM mc = mS;
 		if (tL < t1) {
@@ -925,7 +950,7 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 		} else {
 			tS = t1;
 		}
-		compute(mc);
+		compute(mc, tl);
 	};
 	for (;;) {
 		body(ra, mA, tA);
@@ -941,7 +966,8 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 	uint32_t rec = tn < t1 ? tile_record_word(meta, tn, lane) : 0u;  // tile tn's record
 	for (;;) {
 		__syncthreads();  // the previous tile's faces have been read from LDS
-		stage(ra, cur);
+		const TL tl = lengths(cur);
+		stage(ra, tl);
 		__syncthreads();
 		const bool more = tn < t1;
 		RM nxt = cur;
@@ -953,7 +979,7 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 			const uint32_t tnn = tk.next(tn);
 			rec = tnn < t1 ? tile_record_word(meta, tnn, lane) : 0u;
 		}
-		compute(cur);
+		compute(cur, tl);
 		if (!more) break;
 		cur = nxt;
 		tn = tk.next(tn);
@@ -1139,8 +1165,20 @@ struct TileMeta {
 // LEN (see advection_regular_pp_kernel): an ext cell's three lengths come
 // from the per-level table LT (in LDS) by its level byte extl[k], an array
 // parallel to ext read coalesced with the ext code; (DCCRGX_LEN_OWN) an own
-// cell's by slvl[slot], a coalesced 1-B load instead of three 8-B ones.  The
-// lengths are put into the same LDS rows with the same bits as the fields'.
+// cell's by slvl[slot], a coalesced 1-B load instead of three 8-B ones.
+// The lengths are not staged (LLVL): LDS keeps the rows rho, vx, vy, vz and
+// one level byte per column, and a face takes its neighbor's lengths from
+// the table row of that byte (one 1-B LDS read more per neighbor, three 8-B
+// rows of T + ecap less; a level bit in the 16-bit face code would save the
+// read, but the codes have no spare bit: 0xffff, 0x8000 | k and indices up to
+// T + ecap use all of them).  39 KB of LDS at config 3's ecap of 523 instead
+// of 62.8 KB and 77 VGPRs: three blocks per CU (DCCRGX_GEN_BLOCKS), as many
+// as the runtime reports for the mesh's ecap - two at the capacity of 1024.
+// The registers come from two things: the second ext set is gone (the ext
+// cells beyond the first T, in few tiles, are loaded at staging), and the
+// per-tile addresses are recomputed per tile (`ti`).  The same length bits
+// reach the same operands, so the densities are bitwise the fields'.
+// DCCRGX_LEN_LDS_GEN=1 or DCCRGX_LEN_OWN=0 keep the seven rows and two blocks.
 template <int MINW, bool REC, bool ONCE, bool LEN>
 __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
     AdvPtrs P, double* __restrict__ rho_out, const uint32_t* __restrict__ tell, uint32_t tplane,
@@ -1150,21 +1188,30 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 #pragma clang fp contract(off)
 	static_assert(!(LEN && (REC || ONCE)), "the length table is for the default kernels only");
 	constexpr bool LOWN = LEN && DCCRGX_LEN_OWN;
+	constexpr bool LLVL = LOWN && !DCCRGX_LEN_LDS_GEN;  // no length rows: a level byte per column
 	constexpr uint32_t T = 512;
-	// [7][T + ecap] doubles (rho vx vy vz lx ly lz); ONCE: 3 x T doubles of
+	constexpr uint32_t NROW = LLVL ? 4 : 7;
+	// [NROW][T + ecap] doubles (rho vx vy vz lx ly lz); ONCE: 3 x T doubles of
 	// +a face fluxes; 2 x T u32 finer-face pairs; ONCE: 3 x T flags; LEN: 96
-	// doubles, the per-level lengths
+	// doubles, the per-level lengths; LLVL: T + ecap level bytes
+	// (adv_tiles_lds restates the size)
 	extern __shared__ double shd[];
 	const uint32_t W = T + ecap;
-	double* shg = shd + 7 * W;
-	uint32_t* shf = reinterpret_cast<uint32_t*>(shd + 7 * W + (ONCE ? 3 * T : 0));
+	double* shg = shd + NROW * W;
+	uint32_t* shf = reinterpret_cast<uint32_t*>(shd + NROW * W + (ONCE ? 3 * T : 0));
 	uint8_t* shok = reinterpret_cast<uint8_t*>(shf + 2 * T);
 	double* lt = reinterpret_cast<double*>(shf + 2 * T);  // (LEN excludes ONCE)
+	uint8_t* shl = reinterpret_cast<uint8_t*>(lt + 96);   // (LLVL)
 	const StaticTiles tk(ntiles);
 	const uint32_t t1 = tk.t1;
 	uint32_t t = tk.first();
 	if (t >= t1) return;  // block-uniform
 	const uint32_t tid = threadIdx.x;
+	// the thread index the per-tile addresses are formed from.  LLVL: made
+	// opaque once per tile, so that the LDS and global addresses derived from
+	// it are recomputed (a few adds) and not held in registers across the
+	// loop: they are the registers between this kernel and 80
+	uint32_t ti = tid;
 	const double* const rho = P.p[0];
 	const double* const lx = P.p[1];
 	const double* const ly = P.p[2];
@@ -1173,6 +1220,8 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 	const double* const vy = P.p[5];
 	const double* const vz = P.p[6];
 	// the register set of the tile being loaded (field order rho vx vy vz lx ly lz)
+	// (LLVL: entries 0..3 only, and no second ext set: the ext cells beyond
+	// the first T, in few tiles, are loaded at staging)
 	double c[7], xa[7], xb[7];
 	uint32_t row[3], fq[2];
 	uint32_t lvc = 0, lva = 0, lvb = 0;  // LEN: the level bytes of c, xa, xb
@@ -1231,27 +1280,27 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 	auto load = [&](const GM& mt) {
 		const uint32_t ts = mt.ts, n = mt.n, e0 = mt.e0, ne = mt.ne, fb = mt.fb, nf = mt.nf;
 		if (tid < n) {
-			load7(ts + tid, c);
+			load7(ts + ti, c);
 			// the tile's face codes, ext list and finer pairs are read once per
 			// sweep: non-temporal, so they do not evict the field lines other
 			// tiles re-read (paired A/B on config 3: 0.1915 -> 0.1865 ms/sweep)
 			// (three planes of codes: one coalesced 4-B load per plane; the
 			// interleaved 12-B records cost ~20 us per sweep on config 3)
-			row[0] = __builtin_nontemporal_load(tell + (ts + tid));
-			row[1] = __builtin_nontemporal_load(tell + tplane + (ts + tid));
-			row[2] = __builtin_nontemporal_load(tell + 2 * tplane + (ts + tid));
+			row[0] = __builtin_nontemporal_load(tell + (ts + ti));
+			row[1] = __builtin_nontemporal_load(tell + tplane + (ts + ti));
+			row[2] = __builtin_nontemporal_load(tell + 2 * tplane + (ts + ti));
 		}
 		if (tid < ne) {
-			load5(__builtin_nontemporal_load(ext + e0 + tid), xa);
-			if (LEN) lva = __builtin_nontemporal_load(extl + e0 + tid);
+			load5(__builtin_nontemporal_load(ext + e0 + ti), xa);
+			if (LEN) lva = __builtin_nontemporal_load(extl + e0 + ti);
 		}
-		if (tid + T < ne) {
+		if (!LLVL && tid + T < ne) {
 			load5(__builtin_nontemporal_load(ext + e0 + tid + T), xb);
 			if (LEN) lvb = __builtin_nontemporal_load(extl + e0 + tid + T);
 		}
 		if (tid < nf) {
 			typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-			const u2v q = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(tfine) + (fb + tid));
+			const u2v q = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(tfine) + (fb + ti));
 			fq[0] = q.x;
 			fq[1] = q.y;
 		}
@@ -1262,25 +1311,34 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 	uint32_t rec = tn < t1 ? tile_record_word(meta, tn, lane) : 0u;  // tile tn's record
 	for (;;) {
 		const uint32_t n = cur.n, ne = cur.ne, nf = cur.nf, ts = cur.ts;
+		if (LLVL) asm volatile("" : "+v"(ti));
 		__syncthreads();  // the previous tile's faces have been read from LDS
 		if (tid < n) {
-			if (LOWN) lengths(lvc, c);
+			if (LOWN && !LLVL) lengths(lvc, c);
 #pragma unroll
-			for (int k = 0; k < 7; k++) shd[k * W + tid] = c[k];
+			for (uint32_t k = 0; k < NROW; k++) shd[k * W + ti] = c[k];
+			if (LLVL) shl[ti] = uint8_t(lvc);
 		}
 		if (tid < ne) {
-			if (LEN) lengths(lva, xa);
+			if (LEN && !LLVL) lengths(lva, xa);
 #pragma unroll
-			for (int k = 0; k < 7; k++) shd[k * W + T + tid] = xa[k];
+			for (uint32_t k = 0; k < NROW; k++) shd[k * W + T + ti] = xa[k];
+			if (LLVL) shl[T + ti] = uint8_t(lva);
 		}
 		if (tid + T < ne) {
-			if (LEN) lengths(lvb, xb);
+			if (LLVL) {
+				load5(__builtin_nontemporal_load(ext + cur.e0 + ti + T), xb);
+				lvb = __builtin_nontemporal_load(extl + cur.e0 + ti + T);
+				shl[2 * T + ti] = uint8_t(lvb);
+			} else if (LEN) {
+				lengths(lvb, xb);
+			}
 #pragma unroll
-			for (int k = 0; k < 7; k++) shd[k * W + 2 * T + tid] = xb[k];
+			for (uint32_t k = 0; k < NROW; k++) shd[k * W + 2 * T + ti] = xb[k];
 		}
 		if (tid < nf) {
-			shf[2 * tid] = fq[0];
-			shf[2 * tid + 1] = fq[1];
+			shf[2 * ti] = fq[0];
+			shf[2 * ti + 1] = fq[1];
 		}
 		const uint32_t r0 = row[0], r1 = row[1], r2 = row[2];
 		__syncthreads();
@@ -1297,16 +1355,29 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 		const bool own = tid < n;
 		double cd = 0, cvx = 0, cvy = 0, cvz = 0, clx = 1, cly = 1, clz = 1;
 		if (own) {
-			cd = shd[tid];
-			cvx = shd[W + tid];
-			cvy = shd[2 * W + tid];
-			cvz = shd[3 * W + tid];
-			clx = shd[4 * W + tid];
-			cly = shd[5 * W + tid];
-			clz = shd[6 * W + tid];
+			cd = shd[ti];
+			cvx = shd[W + ti];
+			cvy = shd[2 * W + ti];
+			cvz = shd[3 * W + ti];
+			if (LLVL) {
+				// own lengths: the table row of the cell's level byte, kept in
+				// registers across the compute phase
+				const uint32_t k = 3u * (uint32_t(shl[ti]) & 31u);
+				clx = lt[k]; cly = lt[k + 1]; clz = lt[k + 2];
+			} else {
+				clx = shd[(4 % NROW) * W + ti];
+				cly = shd[(5 % NROW) * W + ti];
+				clz = shd[(6 % NROW) * W + ti];
+			}
 		}
 		auto fetch = [&](uint32_t li, int d) -> AdvNb {
-			return AdvNb{shd[li], shd[4 * W + li], shd[5 * W + li], shd[6 * W + li], shd[(1 + (d >> 1)) * W + li]};
+			if (LLVL) {
+				// a neighbor's lengths: the table row of its column's level byte
+				const uint32_t k = 3u * (uint32_t(shl[li]) & 31u);
+				return AdvNb{shd[li], lt[k], lt[k + 1], lt[k + 2], shd[(1 + (d >> 1)) * W + li]};
+			}
+			return AdvNb{shd[li], shd[(4 % NROW) * W + li], shd[(5 % NROW) * W + li], shd[(6 % NROW) * W + li],
+			             shd[(1 + (d >> 1)) * W + li]};
 		};
 		const uint32_t rr[3] = {r0, r1, r2};
 		// ONCE, pass 1: the +a faces to a cell of the tile (direct codes)
@@ -1356,7 +1427,7 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 					acc += adv_face_flux_d(d, cd, clx, cly, clz, cvx, cvy, cvz, fetch(code, d), dt);
 				}
 			}
-			st_nt(rho_out, ts + tid, cd + acc / (clx * cly * clz));
+			st_nt(rho_out, ts + ti, cd + acc / (clx * cly * clz));
 		}
 		if (!more) break;
 		cur = nxt;
@@ -2070,9 +2141,11 @@ void k_advection(const double* const f[7], double* rho_out, const uint32_t* face
 
 // Tiled advection sweep of one run (0 inner, 1 outer): the regular tiles with
 // advection_regular_pp_kernel, every other tile with advection_tiles_pp_kernel,
-// both persistent with two blocks per CU (r01k: one / two tiles in flight per
-// block, dynamic tickets and a second stream for the general sweep all tie
-// or lose against this schedule).
+// both persistent: the field-reading kernels and the experiment variants with
+// two blocks per CU (r01k: one / two tiles in flight per block, dynamic
+// tickets and a second stream for the general sweep all tie or lose against
+// this schedule), the length-table kernels with the blocks per CU the runtime
+// reports for them, three on config 3 (adv_sweep_launch).
 void k_advection_ell(const double* const f[7], double* rho_out, const int32_t* ell, const int32_t* fine, size_t s0,
                      size_t s1, double dt, hipStream_t s, const BandArgs* bands) {
 	if (s1 <= s0) return;
@@ -2087,6 +2160,82 @@ void k_advection_ell(const double* const f[7], double* rho_out, const int32_t* e
 		advection_ell_lds_kernel<false><<<grid_for(s1 - s0, 256, 256u * 64u), 256, 0, s>>>(
 		    f[0], f[1], f[2], f[3], f[4], f[5], f[6], rho_out, ell, fine, s0, s1, dt, BandArgs{});
 	HIP_CHECK(hipGetLastError());
+}
+
+// The two persistent kernels of k_advection_tiles and how they are launched.
+// The length-table kernels are compiled for DCCRGX_REG_BLOCKS /
+// DCCRGX_GEN_BLOCKS blocks per CU; the grid is sized by the blocks per CU the
+// runtime reports for the kernel and its LDS (registers, LDS and a large
+// ecap all enter there), never by a constant.  Should more blocks fit than
+// the kernel is compiled for (an A/B build with fewer), its dynamic LDS is
+// grown until they do not: a persistent grid smaller than the machine's
+// capacity would otherwise be spread unevenly over the CUs.
+constexpr int kRegWaves = 2 * DCCRGX_REG_BLOCKS, kGenWaves = 2 * DCCRGX_GEN_BLOCKS;
+constexpr bool kLvlRow = DCCRGX_LEN_OWN && !DCCRGX_LEN_LDS_GEN;
+
+static bool adv_face_once() {
+	// DCCRGX_FACE_ONCE=1: in-tile same-level faces evaluated once (lost
+	// its paired A/B: 0.184 -> 0.194 ms per sweep, the extra barrier costs
+	// more than the halved flux arithmetic)
+	static const char* fo = std::getenv("DCCRGX_FACE_ONCE");
+	return fo && fo[0] == '1';
+}
+
+// dynamic LDS of advection_tiles_pp_kernel (restates the kernel's layout)
+static size_t adv_tiles_lds(uint32_t ecap, bool once, bool len) {
+	const size_t W = size_t(512) + ecap;
+	const bool lvl_row = len && kLvlRow;
+	return (lvl_row ? 4 : 7) * W * sizeof(double) + size_t(2) * 512 * sizeof(uint32_t) +
+	       (once ? size_t(3) * 512 * (sizeof(double) + 1) : 0) + (len ? 96 * sizeof(double) : 0) +
+	       (lvl_row ? (W + 7) / 8 * 8 : 0);
+}
+
+const Grid::SweepLaunch& adv_sweep_launch(Grid& g, int kind, bool nbrec, bool lentab) {
+	const void* fn;
+	size_t lds_min = 0;
+	int cap = 2;
+	bool table;  // a length-table kernel (the others keep their fixed two blocks per CU)
+	if (kind == 0) {
+		if (nbrec) fn = reinterpret_cast<const void*>(advection_regular_pp_kernel<4, true, false>);
+		else if (lentab) fn = reinterpret_cast<const void*>(advection_regular_pp_kernel<kRegWaves, false, true>);
+		else fn = reinterpret_cast<const void*>(advection_regular_pp_kernel<4, false, false>);
+		table = !nbrec && lentab;
+		if (table) cap = DCCRGX_REG_BLOCKS;
+	} else {
+		const bool once = adv_face_once(), len = lentab && !nbrec && !once;
+		if (nbrec && once) fn = reinterpret_cast<const void*>(advection_tiles_pp_kernel<4, true, true, false>);
+		else if (nbrec) fn = reinterpret_cast<const void*>(advection_tiles_pp_kernel<4, true, false, false>);
+		else if (once) fn = reinterpret_cast<const void*>(advection_tiles_pp_kernel<4, false, true, false>);
+		else if (len) fn = reinterpret_cast<const void*>(advection_tiles_pp_kernel<kGenWaves, false, false, true>);
+		else fn = reinterpret_cast<const void*>(advection_tiles_pp_kernel<4, false, false, false>);
+		lds_min = adv_tiles_lds(uint32_t(g.max_ext), once, len);
+		table = len;
+		if (table) cap = DCCRGX_GEN_BLOCKS;
+	}
+	Grid::SweepLaunch& L = g.adv_launch[kind];
+	if (L.fn == fn && L.lds_min == lds_min && L.blocks_per_cu > 0) return L;
+	int k = 2;
+	size_t lds = lds_min;
+	if (table) {
+		HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, fn, 512, lds));
+		if (k > cap) {
+			hipFuncAttributes fa;
+			HIP_CHECK(hipFuncGetAttributes(&fa, fn));
+			int dev = 0, cu_lds = 0;
+			HIP_CHECK(hipGetDevice(&dev));
+			HIP_CHECK(hipDeviceGetAttribute(&cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
+			// just over a (cap + 1)-th of the CU's LDS per block
+			const size_t per = (size_t(cu_lds) / size_t(cap + 1) + 512) / 512 * 512;
+			if (per > fa.sharedSizeBytes + lds) lds = per - fa.sharedSizeBytes;
+			HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, fn, 512, lds));
+		}
+		DX_REQUIRE(k >= 1, "the tile sweep kernel does not fit a CU");
+	}
+	L.fn = fn;
+	L.lds_min = lds_min;
+	L.lds = lds;
+	L.blocks_per_cu = k;
+	return L;
 }
 
 void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int run, double dt, hipStream_t s,
@@ -2120,31 +2269,28 @@ void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int r
 			const unsigned nblk = unsigned(std::min<size_t>(size_t(256) * 3, (n_reg + 7) / 8 * 8));
 			advection_regular3_kernel<6><<<nblk, 512, 0, s>>>(P, rho_out, meta, uint32_t(n_reg), dt);
 		} else {
-			const unsigned nblk = unsigned(std::min<size_t>(size_t(256) * 2, (n_reg + 7) / 8 * 8));
+			const Grid::SweepLaunch& L = adv_sweep_launch(g, 0, nbrec != nullptr, lentab != nullptr);
+			const unsigned nblk = unsigned(std::min<size_t>(size_t(256) * L.blocks_per_cu, (n_reg + 7) / 8 * 8));
 			if (nbrec)
-				advection_regular_pp_kernel<4, true, false><<<nblk, 512, 0, s>>>(P, rho_out, meta, uint32_t(n_reg), dt,
-				                                                                 nbrec, g.n_slots, nullptr);
+				advection_regular_pp_kernel<4, true, false><<<nblk, 512, L.lds, s>>>(P, rho_out, meta, uint32_t(n_reg),
+				                                                                     dt, nbrec, g.n_slots, nullptr);
 			else if (lentab)
-				advection_regular_pp_kernel<4, false, true><<<nblk, 512, 0, s>>>(P, rho_out, meta, uint32_t(n_reg), dt,
-				                                                                 nullptr, 0, lentab);
+				advection_regular_pp_kernel<kRegWaves, false, true><<<nblk, 512, L.lds, s>>>(
+				    P, rho_out, meta, uint32_t(n_reg), dt, nullptr, 0, lentab);
 			else
-				advection_regular_pp_kernel<4, false, false><<<nblk, 512, 0, s>>>(P, rho_out, meta, uint32_t(n_reg), dt,
-				                                                                  nullptr, 0, nullptr);
+				advection_regular_pp_kernel<4, false, false><<<nblk, 512, L.lds, s>>>(P, rho_out, meta, uint32_t(n_reg),
+				                                                                      dt, nullptr, 0, nullptr);
 		}
 		HIP_CHECK(hipGetLastError());
 	}
 	if (n_irr) {
 		const TileMeta* meta = reinterpret_cast<const TileMeta*>(g.tmeta.p) + (run == 0 ? 0 : g.tcount[2]);
 		const uint32_t ecap = uint32_t(g.max_ext);
-		// DCCRGX_FACE_ONCE=1: in-tile same-level faces evaluated once (lost
-		// its paired A/B: 0.184 -> 0.194 ms per sweep, the extra barrier costs
-		// more than the halved flux arithmetic)
-		static const char* fo = std::getenv("DCCRGX_FACE_ONCE");
-		const bool once = fo && fo[0] == '1';
+		const bool once = adv_face_once();
 		const bool len = lentab && !nbrec && !once;  // the length table: the default kernel only
-		const size_t lds = size_t(7) * (512 + ecap) * sizeof(double) + size_t(2) * 512 * sizeof(uint32_t) +
-		                   (once ? size_t(3) * 512 * (sizeof(double) + 1) : 0) + (len ? 96 * sizeof(double) : 0);
-		const unsigned nblk = unsigned(std::min<size_t>(size_t(256) * 2, (n_irr + 7) / 8 * 8));
+		const Grid::SweepLaunch& L = adv_sweep_launch(g, 1, nbrec != nullptr, lentab != nullptr);
+		const size_t lds = L.lds;
+		const unsigned nblk = unsigned(std::min<size_t>(size_t(256) * L.blocks_per_cu, (n_irr + 7) / 8 * 8));
 		const uint32_t tp = uint32_t(g.n_local + 1);
 		if (nbrec && once)
 			advection_tiles_pp_kernel<4, true, true, false><<<nblk, 512, lds, s>>>(
@@ -2159,7 +2305,7 @@ void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int r
 			    P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt, nullptr, 0, nullptr,
 			    nullptr, nullptr);
 		else if (len)
-			advection_tiles_pp_kernel<4, false, false, true><<<nblk, 512, lds, s>>>(
+			advection_tiles_pp_kernel<kGenWaves, false, false, true><<<nblk, 512, lds, s>>>(
 			    P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt, nullptr, 0, g.slot_lvl.p,
 			    g.ext_lvl.p, lentab);
 		else

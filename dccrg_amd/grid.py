@@ -912,7 +912,22 @@ class Dccrg:
         check(lib().dccrgx_advection_layout(self.h, out))
         keys = ("tile", "tiles", "ext_total", "ext_max", "finer_faces", "face_entries", "alg_bytes",
                 "alg_bytes_core", "regular_tiles", "regular_cells", "ext_regular", "bytes_needed")
-        return dict(zip(keys, (int(v) for v in out)))
+        lay = dict(zip(keys, (int(v) for v in out)))
+        occ = self.advection_occupancy()
+        lay["regular_blocks_per_cu"] = occ["regular"]["blocks_per_cu"]
+        lay["general_blocks_per_cu"] = occ["general"]["blocks_per_cu"]
+        return lay
+
+    def advection_occupancy(self):
+        """Per tile kernel ("regular", "general") the blocks per CU its
+        persistent grid is launched with, what the runtime's occupancy query
+        reports for that kernel and LDS size, and the dynamic LDS bytes
+        (see include/dccrgx.h)."""
+        out = (C.c_uint64 * 6)()
+        check(lib().dccrgx_advection_occupancy(self.h, out))
+        v = [int(x) for x in out]
+        keys = ("blocks_per_cu", "blocks_per_cu_query", "lds_bytes")
+        return {"regular": dict(zip(keys, v[0:3])), "general": dict(zip(keys, v[3:6]))}
 
     def advection_check_adaptation(self, density, diff_increase, diff_threshold=0.25, unrefine_sensitivity=0.5):
         """check_for_adaptation (tests/advection/adapter.hpp:47-178) + the

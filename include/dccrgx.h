@@ -524,6 +524,17 @@ int dccrgx_advection_adapt(dccrgx_grid* g, const int fields[7], uint64_t out[2])
  * No reference counterpart (roofline introspection). */
 int dccrgx_advection_layout(dccrgx_grid* g, uint64_t out[12]);
 
+/* How the tile sweep of the fields last passed to an advection call launches
+ * its two persistent kernels: out[0] the blocks per CU the regular tiles'
+ * kernel is launched with (its grid is min(CUs x that, tiles rounded up to
+ * 8)), [1] the blocks per CU the runtime's occupancy query reports now for
+ * that kernel at the dynamic LDS size it is launched with, [2] that size in
+ * bytes; [3..5] the same for the kernel of all other tiles.  The sweeps that
+ * take the cell lengths from the per-level table size their grids by the
+ * query, so [0] == [1] and [3] == [4] there; the field-reading sweeps and the
+ * experiment variants are launched with two.  No reference counterpart. */
+int dccrgx_advection_occupancy(dccrgx_grid* g, uint64_t out[6]);
+
 /* Where the tile sweeps of fields fids (density, vx, vy, vz, lx, ly, lz) take
  * the cell lengths from: *out = 1 the per-level table l0[d] * 2^-level (every
  * slot's three lengths, remote copies included, were compared bitwise with
