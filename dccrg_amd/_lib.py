@@ -54,6 +54,9 @@ _SIGS = {
     "dccrgx_initialize": (C.c_int, [vp]),
     "dccrgx_set_geometry": (C.c_int, [vp, P(C.c_double), P(C.c_double)]),
     "dccrgx_geometry_batch": (C.c_int, [vp, vp, sz, vp, vp]),
+    "dccrgx_set_stretched_geometry": (C.c_int, [vp, P(vp), P(sz)]),
+    "dccrgx_get_stretched_geometry": (C.c_int, [vp, C.c_int, vp, sz, P(sz)]),
+    "dccrgx_geometry_fill": (C.c_int, [vp, P(C.c_int), P(C.c_int)]),
     "dccrgx_get_cell_from_indices": (u64, [vp, P(u64), C.c_int]),
     "dccrgx_get_indices": (C.c_int, [vp, u64, P(u64)]),
     "dccrgx_get_refinement_level": (C.c_int, [vp, u64]),

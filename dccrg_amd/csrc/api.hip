@@ -534,6 +534,7 @@ static void start_load_impl(Grid& g, const char* path, uint64_t offset, size_t h
 	g.R = R;
 	g.hood_len = hood;
 	g.geo_block = std::move(geo);
+	g.str.drop();
 	init_impl(g);
 	uint64_t total = 0;
 	pread_all(fd, &total, 8, off);
@@ -1157,6 +1158,73 @@ int dccrgx_set_geometry(dccrgx_grid* gp, const double start[3], const double l0[
 			g.start[d] = start[d];
 			g.l0[d] = l0[d];
 		}
+		// back to Cartesian: the coordinates and the block made from them go
+		// (a block given through dccrgx_set_geometry_block stays)
+		if (g.str.active) {
+			g.str.drop();
+			g.geo_block.clear();
+		}
+		return 0;
+	});
+}
+
+int dccrgx_set_stretched_geometry(dccrgx_grid* gp, const double* const coords[3], const size_t n[3]) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		DX_REQUIRE(coords && n, "null pointer");
+		// dccrg_stretched_cartesian_geometry.hpp:172-210
+		for (int d = 0; d < 3; d++) {
+			const std::string dim = " in dimension " + std::to_string(d);
+			DX_REQUIRE(coords[d] != nullptr, "null coordinates" + dim);
+			DX_REQUIRE(n[d] >= 2, "at least two coordinates are required" + dim);
+			DX_REQUIRE(n[d] == g.len[d] + 1, "the number of coordinates" + dim + " must be the grid's length + 1 (" +
+			                                     std::to_string(g.len[d] + 1) + ") but is " + std::to_string(n[d]));
+			for (size_t i = 0; i < n[d]; i++)
+				DX_REQUIRE(std::isfinite(coords[d][i]), "coordinates must be finite" + dim);
+			for (size_t i = 0; i + 1 < n[d]; i++)
+				DX_REQUIRE(coords[d][i] < coords[d][i + 1], "coordinates must be strictly increasing" + dim);
+		}
+		g.str.drop();
+		g.str.active = true;
+		// the grid file's block (write 652-715): int id 2, the three counts, the coordinates
+		std::vector<uint8_t>& b = g.geo_block;
+		b.resize(28 + 8 * (n[0] + n[1] + n[2]));
+		const int32_t gid = kStretchedGeometryId;
+		std::memcpy(b.data(), &gid, 4);
+		size_t at = 28;
+		for (int d = 0; d < 3; d++) {
+			g.str.c[d].assign(coords[d], coords[d] + n[d]);
+			const uint64_t cnt = n[d];
+			std::memcpy(b.data() + 4 + 8 * d, &cnt, 8);
+			std::memcpy(b.data() + at, coords[d], 8 * n[d]);
+			at += 8 * n[d];
+			// what the consumers that stay Cartesian see, as after load_grid_data:
+			// the start and the first level-0 cell's length
+			g.start[d] = coords[d][0];
+			g.l0[d] = coords[d][1] - coords[d][0];
+		}
+		return 0;
+	});
+}
+
+int dccrgx_get_stretched_geometry(dccrgx_grid* gp, int dim, double* out, size_t cap, size_t* n) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		DX_REQUIRE(n != nullptr, "null count");
+		DX_REQUIRE(dim >= 0 && dim < 3, "dimension must be 0, 1 or 2");
+		const std::vector<double>& c = g.str.c[dim];
+		*n = g.str.active ? c.size() : 0;
+		if (!out || !*n) return 0;
+		DX_REQUIRE(cap >= c.size(), "buffer too small for the coordinates");
+		std::memcpy(out, c.data(), c.size() * 8);
+		return 0;
+	});
+}
+
+int dccrgx_geometry_fill(dccrgx_grid* gp, const int center_fields[3], const int length_fields[3]) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		geometry_fill(g, center_fields, length_fields);
 		return 0;
 	});
 }
@@ -1177,12 +1245,14 @@ int dccrgx_set_geometry_block(dccrgx_grid* gp, const void* bytes, size_t n) {
 		GRID_OR_FAIL(gp);
 		if (n == 0) {
 			g.geo_block.clear();
+			g.str.drop();
 			return 0;
 		}
 		DX_REQUIRE(bytes != nullptr && n >= 28, "geometry block too short");
 		const uint8_t* b = static_cast<const uint8_t*>(bytes);
 		DX_REQUIRE(stretched_block_bytes(b) == n, "not a Stretched_Cartesian_Geometry block (id 2, counts, coordinates)");
 		g.geo_block.assign(b, b + n);
+		g.str.drop();  // a file block only: no device geometry
 		return 0;
 	});
 }
@@ -1203,6 +1273,8 @@ int dccrgx_geometry_batch(dccrgx_grid* gp, const uint64_t* ids, size_t n, double
 	return guard([&] {
 		GRID_OR_FAIL(gp);
 		DX_REQUIRE(ids || !n, "null ids");
+		for (int d = 0; d < 3 && g.str.active; d++)
+			DX_REQUIRE(g.str.c[d].size() == g.len[d] + 1, "the grid's length changed after set_stretched_geometry");
 		MapCtx m;
 		map_init(m, g.len, g.R, g.per);
 		const double nan = std::numeric_limits<double>::quiet_NaN();
@@ -1211,7 +1283,13 @@ int dccrgx_geometry_batch(dccrgx_grid* gp, const uint64_t* ids, size_t n, double
 			const int lvl = map_indices(m, ids[i], ind[0], ind[1], ind[2]);
 			for (int d = 0; d < 3; d++) {
 				double L = nan, c = nan;
-				if (lvl >= 0) {  // dccrg_cartesian_geometry.hpp:299-303, 334-359
+				if (lvl >= 0 && g.str.active) {  // dccrg_stretched_cartesian_geometry.hpp:298-337, 346-403
+					const std::vector<double>& x = g.str.c[d];
+					const uint64_t l0i = uint64_t(1) << g.R, i0 = ind[d] / l0i;
+					L = (x[i0 + 1] - x[i0]) / double(uint64_t(1) << lvl);
+					const double length_of_index = (x[i0 + 1] - x[i0]) / double(l0i);
+					c = x[i0] + length_of_index * double(ind[d] - i0 * l0i) + L / 2;
+				} else if (lvl >= 0) {  // dccrg_cartesian_geometry.hpp:299-303, 334-359
 					L = g.l0[d] * (1.0 / double(uint64_t(1) << lvl));
 					c = g.start[d] + double(ind[d]) * g.l0[d] / double(uint64_t(1) << g.R) + L / 2;
 				}

@@ -46,5 +46,11 @@ bool gol_slab_plan(Grid& g, std::vector<GolBox>& inner, std::vector<GolBox>& out
 // of K-double particle records (stats: stayed, moved, arrived, handed over, lost)
 void existing_cells_at(Grid& g, const double* xyz, size_t n, uint64_t* ids);
 void particles_step(Grid& g, int fid, int K, const double* velocity, double dt, uint64_t stats[5]);
+// the active stretched geometry's coordinates on the device (x, then y, then
+// z, packed), uploaded at first use
+const double* stretched_device(Grid& g);
+// geometry.hip: the fp64 center and / or length of every slot's cell into
+// fixed-size fp64 fields (-1: none), Cartesian or stretched
+void geometry_fill(Grid& g, const int center_fields[3], const int length_fields[3]);
 
 }  // namespace dccrgx

@@ -556,6 +556,22 @@ struct Grid {
 	// save_grid_data instead of start / l0, read back by load_grid_data
 	// (dccrgx_set_geometry_block / dccrgx_get_geometry_block); empty: Cartesian
 	std::vector<uint8_t> geo_block;
+	// Stretched_Cartesian_Geometry on the device (dccrgx_set_stretched_geometry):
+	// per dimension the len[d] + 1 level-0 cell boundaries.  While active,
+	// geo_block is the block made from them; a block given any other way
+	// (dccrgx_set_geometry_block, load_grid_data) leaves this inactive.  The
+	// device copy is one packed array (x, then y, then z), made at first use.
+	struct Stretched {
+		bool active = false;
+		std::vector<double> c[3];
+		DBuf<double> dev;
+		bool dev_valid = false;
+		void drop() {
+			active = false;
+			dev_valid = false;
+			for (auto& v : c) v.clear();
+		}
+	} str;
 
 	Mesh mesh;
 	std::unordered_map<uint64_t, int> pins;  // local cells pinned to a process (pin 5832-5909)

@@ -7,7 +7,12 @@
 // Cartesian_Geometry::get_real_coordinate / get_indices(coordinate)
 // (dccrg_cartesian_geometry.hpp:521-607) and the finest-first probe of
 // get_existing_cell(indices, 0, R) (dccrg.hpp:11275-11308); the batch query
-// and the particle step both call it.
+// and the particle step both call it.  Under a stretched geometry
+// (dccrgx_set_stretched_geometry) a second one restates
+// Stretched_Cartesian_Geometry::get_real_coordinate / get_indices
+// (dccrg_stretched_cartesian_geometry.hpp:504-607) with the reference's two
+// linear scans replaced by a binary search and a corrected quotient that give
+// the same indices; the Cartesian kernels are instantiated without it.
 //
 // The step (DESIGN.md "Particles"):
 //   1. locate  - a thread per particle: source slot (search of the record
@@ -25,6 +30,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
+#include <type_traits>
 
 #include "dccrgx_grid.hpp"
 
@@ -105,6 +111,101 @@ __device__ __forceinline__ uint64_t existing_cell_at(const MapCtx& m, const DevM
 	return error_cell;
 }
 
+// Stretched_Cartesian_Geometry (Grid::str): the packed level-0 boundaries of
+// the three dimensions (dimension d at c + off[d], n[d] of them); g holds
+// start = c[0], end = c[n - 1] and the periodicity, l0 = 2^R
+struct SGeo {
+	PGeo g;
+	const double* c;
+	uint32_t off[3], n[3];
+	uint32_t total;
+	double l0;
+};
+
+// the three coordinate lists are searched in LDS when together they are at
+// most this many doubles (12 KiB: with the 4 KiB of record offsets a block of
+// the locate kernel stays at 16 KiB, eight blocks a CU as before), else in
+// global memory
+constexpr uint32_t kCoordCache = 1536;
+
+// get_indices of one dimension (dccrg_stretched_cartesian_geometry.hpp:575-602)
+// for a coordinate inside [c[0], c[n - 1]].  The level-0 cell: the reference
+// scans for the first boundary >= x and steps one back (a boundary belongs to
+// the cell below it; x == c[0] to cell 0, the facade's host get_indices).  The
+// offset inside it: the reference counts k up while c0 + k * li < x; the sum
+// never decreases with k, so floor((x - c0) / li) corrected by that predicate
+// is the same k.  li resolves at both ends of the cell (stretched_device
+// checks it), so each loop runs a step or two.
+__device__ __forceinline__ uint64_t stretched_index(const double* c, uint32_t n, double l0, double x) {
+	uint32_t lo = 0, hi = n - 1;  // c[n - 1] >= x
+	while (lo < hi) {
+		const uint32_t mid = lo + (hi - lo) / 2;
+		if (c[mid] >= x)
+			hi = mid;
+		else
+			lo = mid + 1;
+	}
+	const uint32_t i0 = lo == 0 ? 0 : lo - 1;
+	const double c0 = c[i0];
+	const double extent = c[i0 + 1] - c0;
+	const double li = extent / l0;
+	const double rel = x - c0;
+	const double q = rel / li;
+	uint64_t k = uint64_t(floor(q));
+	while (true) {
+		const double w = double(k) * li;
+		if (!(c0 + w < x)) break;
+		k++;
+	}
+	while (k > 0) {
+		const double w = double(k - 1) * li;
+		if (!(c0 + w >= x)) break;
+		k--;
+	}
+	return uint64_t(i0) * uint64_t(l0) + (k == 0 ? 0 : k - 1);
+}
+
+// existing_cell_at under the stretched geometry; c: the packed coordinates
+// (S.c, or a block's copy in LDS)
+__device__ __forceinline__ uint64_t stretched_cell_at(const MapCtx& m, const DevMesh& M, const SGeo& S,
+                                                      const double* c, const double x[3]) {
+	uint64_t ind[3];
+#pragma unroll
+	for (int d = 0; d < 3; d++) {
+		const double r = real_coordinate(S.g, d, x[d]);
+		if (!(r >= S.g.start[d] && r <= S.g.end[d])) return error_cell;
+		ind[d] = stretched_index(c + S.off[d], S.n[d], S.l0, r);
+		// the reference's rounding quirk: a point at a level-0 cell's upper
+		// boundary may index the next cell's first index, in the last cell one
+		// past the grid (get_existing_cell(indices), dccrg.hpp:11280-11290)
+		if (ind[d] >= m.glen[d]) return error_cell;
+	}
+	for (int lvl = m.R; lvl >= 0; lvl--) {
+		const uint64_t id = map_from_indices(m, ind[0], ind[1], ind[2], lvl);
+		if (known_leaf(M, id)) return id;
+	}
+	return error_cell;
+}
+
+// a block's copy of the coordinates (the caller syncs); false: they do not fit
+__device__ __forceinline__ bool stage_coordinates(const SGeo& S, double* s_c) {
+	if (S.total > kCoordCache) return false;
+	for (uint32_t i = threadIdx.x; i < S.total; i += blockDim.x) s_c[i] = S.c[i];
+	return true;
+}
+
+__global__ __launch_bounds__(256) void stretched_cells_at_kernel(const MapCtx m, const DevMesh M, const SGeo S,
+                                                                    const double* __restrict__ xyz, size_t n,
+                                                                    uint64_t* __restrict__ ids) {
+	__shared__ double s_c[kCoordCache];
+	const bool cached = stage_coordinates(S, s_c);
+	__syncthreads();
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
+		const double x[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+		ids[i] = cached ? stretched_cell_at(m, M, S, s_c, x) : stretched_cell_at(m, M, S, S.c, x);
+	}
+}
+
 __global__ void cells_at_kernel(const MapCtx m, const DevMesh M, const PGeo G, const double* __restrict__ xyz, size_t n,
                                 uint64_t* __restrict__ ids) {
 	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
@@ -168,10 +269,24 @@ struct PArgs {
 	uint32_t* part;           // per block: moved, arrived, handed over, lost
 };
 
-__global__ __launch_bounds__(kPB) void particles_locate_kernel(const MapCtx m, const DevMesh M, const PGeo G,
+__device__ __forceinline__ const PGeo& wrap_geo(const PGeo& G) { return G; }
+__device__ __forceinline__ const PGeo& wrap_geo(const SGeo& S) { return S.g; }
+
+// Geo: PGeo (Cartesian) or SGeo (stretched: the coordinates staged in LDS
+// once per block when they fit)
+template <class Geo>
+__global__ __launch_bounds__(kPB) void particles_locate_kernel(const MapCtx m, const DevMesh M, const Geo G,
                                                                   const PArgs a) {
+	constexpr bool kStretched = std::is_same<Geo, SGeo>::value;
 	__shared__ uint32_t s_off[kOffCache];
 	__shared__ uint32_t s_cnt[4];
+	double* s_c = nullptr;
+	bool coords_cached = false;
+	if constexpr (kStretched) {
+		__shared__ double s_coords[kCoordCache];
+		s_c = s_coords;
+		coords_cached = stage_coordinates(G, s_c);  // synced by the first pass below
+	}
 	uint32_t n_moved = 0, n_arrived = 0, n_handed = 0, n_lost = 0;
 	if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
 	const size_t chunks = (a.N + kPB - 1) / kPB;
@@ -196,10 +311,14 @@ __global__ __launch_bounds__(kPB) void particles_locate_kernel(const MapCtx m, c
 			const double v = a.has_vel ? a.vel[d] : r[3 + d];
 			const double step = v * a.dt;
 			const double moved = r[d] + step;
-			x[d] = real_coordinate(G, d, moved);
+			x[d] = real_coordinate(wrap_geo(G), d, moved);
 			r[d] = x[d];
 		}
-		const uint64_t dst = existing_cell_at(m, M, G, x);
+		uint64_t dst;
+		if constexpr (kStretched)
+			dst = coords_cached ? stretched_cell_at(m, M, G, s_c, x) : stretched_cell_at(m, M, G, G.c, x);
+		else
+			dst = existing_cell_at(m, M, G, x);
 		const uint64_t own = a.slot_ids[s];
 		const bool local = s < a.n_local;
 		int32_t dest = -1;
@@ -352,15 +471,66 @@ int bits_for(size_t n) {  // every value < n fits in this many bits (at least 1)
 	return b;
 }
 
-void require_cartesian(const Grid& g) {
+// Cartesian, or stretched with its coordinates given (Grid::str); a geometry
+// block that is only a grid file's bytes has no device geometry
+void require_geometry(const Grid& g) {
 	DX_REQUIRE(g.initialized, "not initialized");
-	DX_REQUIRE(g.geo_block.empty(), "the grid holds a stretched geometry block (Cartesian geometry only)");
+	DX_REQUIRE(g.str.active || g.geo_block.empty(),
+	           "the grid holds a stretched geometry block (Cartesian geometry only)");
+}
+
+SGeo make_sgeo(Grid& g) {
+	SGeo S;
+	S.c = stretched_device(g);
+	uint32_t at = 0;
+	for (int d = 0; d < 3; d++) {
+		const auto& c = g.str.c[d];
+		S.off[d] = at;
+		S.n[d] = uint32_t(c.size());
+		at += S.n[d];
+		S.g.start[d] = c.front();
+		S.g.end[d] = c.back();
+		S.g.cell[d] = 0;
+		S.g.per[d] = g.per[d];
+	}
+	S.total = at;
+	S.l0 = double(uint64_t(1) << g.R);
+	return S;
 }
 
 }  // namespace
 
+// the packed device copy of the coordinates, made at first use.  The finest
+// cells must be resolvable at both ends of their level-0 cell (c + li != c):
+// the point location's correction loops then end after a step or two.
+const double* stretched_device(Grid& g) {
+	Grid::Stretched& T = g.str;
+	DX_REQUIRE(T.active, "no stretched geometry");
+	DX_REQUIRE(g.initialized, "not initialized");
+	if (T.dev_valid) return T.dev.p;
+	std::vector<double> h;
+	const double l0 = double(uint64_t(1) << g.R);
+	for (int d = 0; d < 3; d++) {
+		const auto& c = T.c[d];
+		DX_REQUIRE(c.size() == g.len[d] + 1, "the grid's length changed after set_stretched_geometry");
+		for (size_t i = 0; i + 1 < c.size(); i++) {
+			const double li = (c[i + 1] - c[i]) / l0;
+			DX_REQUIRE(li > 0 && c[i] + li > c[i] && c[i + 1] - li < c[i + 1],
+			           "stretched geometry: the finest cells of dimension " + std::to_string(d) +
+			               " are below the resolution of their coordinates");
+		}
+		h.insert(h.end(), c.begin(), c.end());
+	}
+	DX_REQUIRE(h.size() < (size_t(1) << 31), "stretched geometry: too many coordinates");
+	T.dev.alloc(h.size());
+	h2d(T.dev.p, h.data(), h.size() * sizeof(double), g.s_comp);
+	HIP_CHECK(hipStreamSynchronize(g.s_comp));  // h is a local
+	T.dev_valid = true;
+	return T.dev.p;
+}
+
 void existing_cells_at(Grid& g, const double* xyz, size_t n, uint64_t* ids) {
-	require_cartesian(g);
+	require_geometry(g);
 	if (!n) return;
 	DX_REQUIRE(xyz && ids, "null pointer");
 	hipStream_t s = g.s_comp;
@@ -369,13 +539,16 @@ void existing_cells_at(Grid& g, const double* xyz, size_t n, uint64_t* ids) {
 	dx.alloc(3 * n);
 	di.alloc(n);
 	h2d(dx.p, xyz, 3 * n * sizeof(double), s);
-	cells_at_kernel<<<grid_for(n, 256), 256, 0, s>>>(g.m, g.dm(), make_geo(g), dx.p, n, di.p);
+	if (g.str.active)
+		stretched_cells_at_kernel<<<grid_for(n, 256), 256, 0, s>>>(g.m, g.dm(), make_sgeo(g), dx.p, n, di.p);
+	else
+		cells_at_kernel<<<grid_for(n, 256), 256, 0, s>>>(g.m, g.dm(), make_geo(g), dx.p, n, di.p);
 	HIP_CHECK(hipGetLastError());
 	d2h_small(ids, di.p, n * sizeof(uint64_t), s);
 }
 
 void particles_step(Grid& g, int fid, int K, const double* velocity, double dt, uint64_t stats[5]) {
-	require_cartesian(g);
+	require_geometry(g);
 	Field& f = field(g, fid);
 	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
 	DX_REQUIRE(K >= 3, "a particle record has at least 3 doubles (the position)");
@@ -442,7 +615,10 @@ void particles_step(Grid& g, int fid, int K, const double* velocity, double dt, 
 	a.stay = stay.p;
 	a.mover = mover.p;
 	a.part = part.p;
-	particles_locate_kernel<<<nb, kPB, 0, s>>>(g.m, g.dm(), make_geo(g), a);
+	if (g.str.active)
+		particles_locate_kernel<SGeo><<<nb, kPB, 0, s>>>(g.m, g.dm(), make_sgeo(g), a);
+	else
+		particles_locate_kernel<PGeo><<<nb, kPB, 0, s>>>(g.m, g.dm(), make_geo(g), a);
 	HIP_CHECK(hipGetLastError());
 	DBuf<uint64_t> dstats;
 	dstats.alloc(4);

@@ -294,9 +294,66 @@ class Dccrg:
         check(lib().dccrgx_get_geometry_block(self.h, buf, n.value, C.byref(n)))
         return buf.raw[: n.value]
 
+    def set_stretched_geometry(self, coords):
+        """Stretched_Cartesian_Geometry as the grid's geometry: per dimension
+        the length + 1 strictly increasing boundaries of the level-0 cells
+        (set_initial_length first).  geometry(), get_existing_cells_at,
+        particles_step and fill_geometry then answer from it; set_geometry
+        returns to Cartesian."""
+        arrs = [np.ascontiguousarray(c, np.float64).ravel() for c in coords]
+        if len(arrs) != 3:
+            raise ValueError("coordinates of three dimensions are needed")
+        ptrs = (C.c_void_p * 3)(*[a.ctypes.data for a in arrs])
+        n = (C.c_size_t * 3)(*[a.size for a in arrs])
+        check(lib().dccrgx_set_stretched_geometry(self.h, ptrs, n))
+        return self
+
+    def stretched_geometry(self):
+        """The three coordinate arrays of the active stretched geometry, or None."""
+        out = []
+        for d in range(3):
+            n = C.c_size_t()
+            check(lib().dccrgx_get_stretched_geometry(self.h, d, None, 0, C.byref(n)))
+            if not n.value:
+                return None
+            a = np.empty(n.value, np.float64)
+            check(lib().dccrgx_get_stretched_geometry(self.h, d, _ptr(a), a.size, C.byref(n)))
+            out.append(a)
+        return out
+
+    def adopt_geometry_block(self):
+        """Make the stretched geometry block this grid holds (a loaded file's,
+        or one given to set_geometry_block) the grid's geometry: its
+        coordinates go to set_stretched_geometry."""
+        b = self.geometry_block()
+        if len(b) < 28 or int(np.frombuffer(b[:4], np.int32)[0]) != 2:
+            raise DccrgError(EINVAL, "the grid holds no stretched geometry block")
+        cnt = [int(x) for x in np.frombuffer(b[4:28], np.uint64)]
+        if len(b) != 28 + 8 * sum(cnt):
+            raise DccrgError(EINVAL, "the stretched geometry block is truncated")
+        c = np.frombuffer(b[28:], np.float64)
+        return self.set_stretched_geometry([c[: cnt[0]], c[cnt[0] : cnt[0] + cnt[1]], c[cnt[0] + cnt[1] :]])
+
+    def fill_geometry(self, center=None, length=None):
+        """The center and / or length of every slot's cell (local cells and
+        remote copies) written into three fp64 Fields each, on the device,
+        under the grid's geometry (Cartesian or stretched).  An entry may be
+        None to skip that component."""
+
+        def ids(fields):
+            if fields is None:
+                return None
+            if len(fields) != 3:
+                raise ValueError("three fields (x, y, z) are needed")
+            return (C.c_int * 3)(*[-1 if f is None else f.id for f in fields])
+
+        check(lib().dccrgx_geometry_fill(self.h, ids(center), ids(length)))
+        return self
+
     def geometry(self, cells):
-        """(centers, lengths), each (n, 3): Cartesian_Geometry get_center /
-        get_length (dccrg_cartesian_geometry.hpp:282-362) of many cells."""
+        """(centers, lengths), each (n, 3): get_center / get_length of many
+        cells, Cartesian_Geometry's (dccrg_cartesian_geometry.hpp:282-362) or,
+        after set_stretched_geometry, Stretched_Cartesian_Geometry's."""
         ids = np.ascontiguousarray(cells, np.uint64)
         c = np.empty((ids.size, 3))
         L = np.empty((ids.size, 3))

@@ -5,12 +5,17 @@ per particle, |v dt| = 0.3 cell lengths, 20 timed steps after warm-up.  Prints
 one JSON line in the style of bench.py's: ms per step, particle-updates/s, the
 algorithmic bytes of the pass structure (Particles) and their
 fraction of the HBM peak, and the time of one VariableField.resize re-lay of
-the same pool in the same run (the library's copy-once yardstick)."""
+the same pool in the same run (the library's copy-once yardstick).
+
+--stretched measures the same grid under a Stretched_Cartesian_Geometry of
+unequal cells (dccrgx_set_stretched_geometry) next to the Cartesian step, and
+records the parent commit's Cartesian lines given with --parent."""
 from __future__ import annotations
 
 import argparse
 import ctypes as C
 import json
+import os
 import time
 
 import numpy as np
@@ -42,44 +47,57 @@ def alg_bytes(n_particles, n_movers, n_cells, hood_entries):
     return n_particles * per_p + n_movers * per_m + rows, per_p, per_m
 
 
-def main(argv=None):
-    p = argparse.ArgumentParser()
-    p.add_argument("--base", type=int, default=128)
-    p.add_argument("--ppc", type=int, default=16)
-    p.add_argument("--steps", type=int, default=20)
-    p.add_argument("--warmup", type=int, default=3)
-    p.add_argument("--out", default=None, help="also write the line to this file")
-    a = p.parse_args(argv)
+def stretched_coordinates(n, seed=7):
+    """Level-0 boundaries of unequal cells: widths 0.5 .. 1.5 in a fixed,
+    seeded pattern of their own per dimension."""
+    rng = np.random.default_rng(seed)
+    return [np.concatenate([[0.0], np.cumsum(0.5 + rng.random(n))]) for _ in range(3)]
 
-    import torch  # noqa: F401  (one HIP runtime for the process)
 
+def measure(a, coords=None):
+    """The timed steps on a fresh grid: Cartesian unit cells, or the stretched
+    geometry of `coords` with the velocity scaled by the mean cell width, so
+    that about the same share of the particles changes cell per step."""
     import dccrg_amd
     from dccrg_amd._lib import check, lib
 
     n = a.base
     g = dccrg_amd.Dccrg(0, 1, 0).set_initial_length((n, n, n)).set_neighborhood_length(1)
     g.set_maximum_refinement_level(0).set_periodic(True, True, True).initialize()
+    velocity = VELOCITY
+    if coords is not None:
+        g.set_stretched_geometry(coords)
+        # the seeded pattern (16 per cell, so denser in narrow cells) drifts through
+        # several cells during the warm-up and the timed steps; averaged over that
+        # drift a boundary sees the mean density, and the share of particles that
+        # cross one per step is v / (mean cell width)
+        velocity = tuple(float(v * np.mean(np.diff(c))) for v, c in zip(VELOCITY, coords))
     fld = g.add_variable_field("particles", np.float64, True)
     ids = g.slot_ids()[: g.n_local]
     nc = ids.size
-    # positions: uniform inside each cell (cell c's min corner from its id, unit cells)
+    # positions: uniform inside each cell (cell c's min corner from its id)
     k = (ids - np.uint64(1)).astype(np.int64)
-    corner = np.stack([k % n, (k // n) % n, k // (n * n)], axis=1).astype(np.float64)
+    ix = np.stack([k % n, (k // n) % n, k // (n * n)], axis=1)
+    if coords is None:
+        corner, width = ix.astype(np.float64), np.ones((nc, 3))
+    else:
+        corner = np.stack([coords[d][ix[:, d]] for d in range(3)], axis=1)
+        width = np.stack([np.diff(coords[d])[ix[:, d]] for d in range(3)], axis=1)
     rng = np.random.default_rng(1)
-    pos = (corner[:, None, :] + rng.random((nc, a.ppc, 3))).reshape(-1)
+    pos = (corner[:, None, :] + width[:, None, :] * rng.random((nc, a.ppc, 3))).reshape(-1)
     counts = np.full(nc, a.ppc * K, np.uint64)
     fld.resize(counts)
     check(lib().dccrgx_variable_field_upload(g.h, fld.id, 0, nc, pos.ctypes.data_as(C.c_void_p), pos.nbytes))
-    del pos, corner
+    del pos, corner, width
     n_particles = nc * a.ppc
 
     for _ in range(a.warmup):
-        st = g.particles_step(fld, K, VELOCITY, 1.0)
+        st = g.particles_step(fld, K, velocity, 1.0)
     g.synchronize()
     movers = 0
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        st = g.particles_step(fld, K, VELOCITY, 1.0)
+        st = g.particles_step(fld, K, velocity, 1.0)
         movers += st["moved"]
     g.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / max(a.steps, 1)
@@ -95,8 +113,34 @@ def main(argv=None):
         g.synchronize()
         relay.append((time.perf_counter() - t0) * 1e3)
     relay_ms = min(relay)
+    g.close()
+    return dict(ms=ms, relay_ms=relay_ms, cells=int(nc), particles=int(n_particles),
+                movers_per_step=movers / max(a.steps, 1))
 
-    m_step = movers / max(a.steps, 1)
+
+def main(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--base", type=int, default=128)
+    p.add_argument("--ppc", type=int, default=16)
+    p.add_argument("--steps", type=int, default=20)
+    p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--out", default=None, help="also write the line to this file")
+    p.add_argument("--stretched", action="store_true",
+                   help="the same grid under a stretched geometry of unequal cells, next to the Cartesian step "
+                        "(--repeats of each, alternating); writes profiles/particles_bench_stretched.json unless --out")
+    p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--parent", default=None,
+                   help="with --stretched: files of lines the parent commit's particles_bench printed in the same "
+                        "machine visit (comma-separated), recorded as the parent's Cartesian step")
+    a = p.parse_args(argv)
+
+    import torch  # noqa: F401  (one HIP runtime for the process)
+
+    if a.stretched:
+        return main_stretched(a)
+    r = measure(a)
+    n, ms, relay_ms, nc, n_particles = a.base, r["ms"], r["relay_ms"], r["cells"], r["particles"]
+    m_step = r["movers_per_step"]
     total, per_p, per_m = alg_bytes(n_particles, m_step, nc, 26)
     ach = total / (ms / 1e3) / 1e9
     line = {"metric": "particles_step", "value": n_particles / (ms / 1e3), "unit": "particle-updates/s", "n_gpus": 1,
@@ -110,12 +154,47 @@ def main(argv=None):
                          "passes": {"per_particle": PER_PARTICLE, "per_mover": PER_MOVER}},
             "relay": {"what": "VariableField.resize of the same pool, sizes unchanged (copy once)",
                       "ms": relay_ms, "step_over_relay": ms / relay_ms}}
-    g.close()
     txt = json.dumps(line)
     print(txt, flush=True)
     if a.out:
         with open(a.out, "w") as f:
             f.write(txt + "\n")
+
+
+def main_stretched(a):
+    """Stretched and Cartesian steps of this tree, alternating, each on a
+    fresh grid; the medians, every run, and the parent commit's Cartesian
+    lines when given."""
+    coords = stretched_coordinates(a.base)
+    runs = {"cartesian": [], "stretched": []}
+    for _ in range(max(a.repeats, 1)):
+        runs["cartesian"].append(measure(a))
+        runs["stretched"].append(measure(a, coords))
+    med = {k: float(np.median([r["ms"] for r in v])) for k, v in runs.items()}
+    n_particles = runs["stretched"][0]["particles"]
+    line = {"metric": "particles_step_stretched", "value": n_particles / (med["stretched"] / 1e3),
+            "unit": "particle-updates/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": med["stretched"], "higher_is_better": True, "dtype": "fp64",
+            "config": {"workload": f"particles in cells, {a.base}^3 periodic, R = 0, neighborhood 1, {a.ppc} per cell, "
+                                   f"K = {K}; stretched: level-0 widths 0.5 .. 1.5 (seeded), the velocity scaled to "
+                                   "the Cartesian run's share of movers",
+                       "coordinates_in_lds": bool(sum(c.size for c in coords) <= 1536), "repeats": a.repeats},
+            "stretched": {"ms_per_step": med["stretched"], "runs": runs["stretched"]},
+            "cartesian": {"ms_per_step": med["cartesian"], "runs": runs["cartesian"]},
+            "stretched_over_cartesian": med["stretched"] / med["cartesian"]}
+    if a.parent:
+        ms = []
+        for path in a.parent.split(","):
+            with open(path) as f:
+                ms += [json.loads(ln)["ms_per_step"] for ln in f if ln.strip()]
+        line["parent_cartesian"] = {"ms_per_step": float(np.median(ms)), "runs_ms": ms}
+        line["cartesian_over_parent"] = med["cartesian"] / float(np.median(ms))
+    txt = json.dumps(line)
+    print(txt, flush=True)
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "particles_bench_stretched.json")
+    with open(out, "w") as f:
+        f.write(txt + "\n")
 
 
 if __name__ == "__main__":

@@ -651,6 +651,9 @@ public:
 		detail::check(dccrgx_set_neighborhood_length(g_, hood_));
 		detail::check(dccrgx_set_load_balancing_method(g_, lb_method_ == "NONE" ? "NONE" : "RCB"));
 		detail::check(dccrgx_initialize(g_));
+		// once more now that the library knows the grid's length: a stretched
+		// geometry's device coordinates are sized by it
+		geometry_rw.set(geometry_rw.get_params_or_default());
 		add_payload_field();
 		refresh();
 		return *this;
@@ -1062,7 +1065,15 @@ public:
 		sync_window();  // the bytes get_mpi_datatype describes now
 		upload_local();
 		const std::vector<char> geo = geometry_rw.file_block();  // Geometry::write's bytes (empty: Cartesian)
-		if (dccrgx_set_geometry_block(g_, geo.empty() ? nullptr : geo.data(), geo.size()) != DCCRGX_OK) return false;
+		// (the library already holds this block when the geometry's device
+		// coordinates made it; giving it again would drop them)
+		size_t held = 0;
+		detail::check(dccrgx_get_geometry_block(g_, nullptr, 0, &held));
+		std::vector<char> cur(held);
+		if (held) detail::check(dccrgx_get_geometry_block(g_, cur.data(), held, &held));
+		if (cur != geo &&
+		    dccrgx_set_geometry_block(g_, geo.empty() ? nullptr : geo.data(), geo.size()) != DCCRGX_OK)
+			return false;
 		return dccrgx_save_grid_data(g_, name.c_str(), offset, header, header_bytes) == DCCRGX_OK;
 	}
 	// the reference's form: the header is (address, count, datatype), written

@@ -11,10 +11,11 @@
  * (get_length 298-337, get_center 346-403), so the doubles are the same.
  * Before the parameters are set (and after initialize without them) the
  * geometry is the reference's reset(): coordinates 0, 1, ..., length.
- * When every dimension's coordinates are evenly spaced (start + i * h, as
- * set(const Cartesian_Geometry&) makes them) the library's device geometry
- * gets that start and h too, so device-side consumers see the same cells;
- * uneven spacing stays host-side.
+ * The library's device geometry gets the same cells: evenly spaced
+ * coordinates (start + i * h, as set(const Cartesian_Geometry&) makes them)
+ * as a Cartesian start and h, uneven ones through
+ * dccrgx_set_stretched_geometry, so get_existing_cell(coordinate) and the
+ * particle step locate points in this geometry.
  * Grid files: save_grid_data writes this geometry's block (write 652-715,
  * file_block) in place of the Cartesian one and load_grid_data reads it back
  * (read 723-800, from_file_block), through dccrgx_set / get_geometry_block.
@@ -256,19 +257,29 @@ private:
 		return r;
 	}
 	bool periodic(size_t d) const { return topology_ && topology_->is_periodic(d); }
-	// evenly spaced coordinates: the library's device geometry takes them too
+	// the library's device geometry: evenly spaced coordinates as a Cartesian
+	// start and cell length, uneven ones as they are
+	// (dccrgx_set_stretched_geometry; refused while the library's grid length
+	// is not set yet: initialize() pushes again once it is)
 	void push_device() const {
 		if (!g_) return;
 		double start[3], h[3];
+		bool even = true;
 		for (size_t d = 0; d < 3; d++) {
 			const auto& c = p_.coordinates[d];
 			if (c.size() < 2) return;
 			start[d] = c[0];
 			h[d] = c[1] - c[0];
 			for (size_t i = 0; i < c.size(); i++)
-				if (c[i] != c[0] + double(i) * h[d]) return;
+				if (c[i] != c[0] + double(i) * h[d]) even = false;
 		}
-		dccrgx_set_geometry(g_, start, h);
+		if (even) {
+			dccrgx_set_geometry(g_, start, h);
+			return;
+		}
+		const double* const c[3] = {p_.coordinates[0].data(), p_.coordinates[1].data(), p_.coordinates[2].data()};
+		const size_t n[3] = {p_.coordinates[0].size(), p_.coordinates[1].size(), p_.coordinates[2].size()};
+		dccrgx_set_stretched_geometry(g_, c, n);
 	}
 
 	Parameters p_;

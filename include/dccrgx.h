@@ -122,6 +122,33 @@ int dccrgx_get_geometry(dccrgx_grid* g, double start[3], double level_0_cell_len
 int dccrgx_set_geometry_block(dccrgx_grid* g, const void* bytes, size_t n);
 int dccrgx_get_geometry_block(dccrgx_grid* g, void* out, size_t cap, size_t* n);
 int dccrgx_geometry_batch(dccrgx_grid* g, const uint64_t* ids, size_t n, double* center, double* length);
+/* Stretched_Cartesian_Geometry as the library's own geometry: per dimension
+ * the level-0 cell boundaries, n[d] == length[d] + 1 (set_initial_length
+ * comes first) finite, strictly increasing values (set 172-210; DCCRGX_EINVAL
+ * otherwise, dccrgx_last_error names the dimension, nothing changes); before
+ * or after initialize.  From then on dccrgx_geometry_batch,
+ * dccrgx_geometry_fill, dccrgx_get_existing_cells_at and dccrgx_particles_step
+ * answer with its get_center / get_length (298-403) and get_real_coordinate /
+ * get_indices (504-607; a coordinate at a dimension's first boundary belongs
+ * to the first cell), the geometry block is the one its write() makes of the
+ * coordinates, and the advection sweeps read the length fields.  The Poisson
+ * factors, dccrgx_advection_initialize and advection_adapt's reset pass stay
+ * Cartesian: they see each dimension's start and first cell length.
+ * dccrgx_set_geometry returns the grid to Cartesian; dccrgx_set_geometry_block
+ * and load_grid_data leave a file block only, without coordinates.  The
+ * finest cells must be wider than the spacing of doubles at their level-0
+ * cell's ends (checked at first device use).
+ * dccrgx_get_stretched_geometry: dimension dim's coordinates (*n = 0 when no
+ * stretched geometry is active; out = NULL: the count only). */
+int dccrgx_set_stretched_geometry(dccrgx_grid* g, const double* const coords[3], const size_t n[3]);
+int dccrgx_get_stretched_geometry(dccrgx_grid* g, int dim, double* out, size_t cap, size_t* n);
+/* The fp64 center and / or length of every slot's cell (local cells and
+ * remote copies) written into fixed-size fp64 fields on the device; either
+ * array may be NULL, an entry -1 skips that component.  Cartesian: the
+ * expressions of dccrgx_advection_initialize, so the lengths are bitwise the
+ * ones it writes.  Stretched: those of dccrgx_geometry_batch.  A field whose
+ * device pointer was handed out is refused. */
+int dccrgx_geometry_fill(dccrgx_grid* g, const int center_fields[3], const int length_fields[3]);
 
 /* ---- mapping (dccrg_mapping.hpp) — host-side scalar queries -------------- */
 uint64_t dccrgx_get_cell_from_indices(dccrgx_grid* g, const uint64_t indices[3], int level); /* 153 */
