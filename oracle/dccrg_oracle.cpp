@@ -1799,6 +1799,17 @@ int or_adv_get(void* hp, const uint64_t* ids, size_t n, double* out9) {
 	})
 }
 
+/* the mirror of or_adv_get: the nine doubles of existing cells (a state other
+   than initialize.hpp's, whose vz is 0 everywhere) */
+int or_adv_set(void* hp, const uint64_t* ids, size_t n, const double* in9) {
+	OR_TRY({
+		auto* h = static_cast<OracleHandle*>(hp);
+		for (size_t i = 0; i < n; i++)
+			for (int k = 0; k < 9; k++) h->adv.at(ids[i]).d[k] = in9[9 * i + k];
+		return 0;
+	})
+}
+
 /* ---- Poisson (tests/poisson/poisson_solve.hpp) ----
    cells: every leaf must be listed once; type 0 solve, 1 boundary, 2 skip
    (the reference's `cells` / default / `cells_to_skip`, 836-878) */

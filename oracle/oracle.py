@@ -85,6 +85,7 @@ def lib():
     L.or_adv_check.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
     L.or_adv_adapt.argtypes = [C.c_void_p, C.c_void_p]
     L.or_adv_get.argtypes = [C.c_void_p, u64p, C.c_size_t, f64p]
+    L.or_adv_set.argtypes = [C.c_void_p, u64p, C.c_size_t, f64p]
     L.or_po_set.argtypes = [C.c_void_p, u64p, f64p, f64p, i32p, C.c_size_t]
     L.or_po_solve.restype = C.c_int64
     L.or_po_solve.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_double, C.c_double, C.c_double, C.c_int,
@@ -328,6 +329,13 @@ class Grid:
         out = np.empty(9 * ids.size)
         self._chk(lib().or_adv_get(self.h, ids, ids.size, out))
         return out.reshape(-1, 9)
+
+    def adv_set(self, ids, cols9):
+        """The mirror of adv_get: the nine doubles of existing cells."""
+        ids = np.ascontiguousarray(ids, np.uint64)
+        cols9 = np.ascontiguousarray(cols9, np.float64).reshape(-1)
+        assert cols9.size == 9 * ids.size
+        self._chk(lib().or_adv_set(self.h, ids, ids.size, cols9))
 
     # ---- Poisson (tests/poisson/poisson_solve.hpp) ----
     PO_FIELDS = ("solution", "best_solution", "p0", "p1", "r0", "r1", "A_dot_p0", "scaling_factor",
