@@ -2415,6 +2415,28 @@ int dccrgx_particles_step(dccrgx_grid* gp, int var_field, int record_doubles, co
 	});
 }
 
+// refined_cell_data (dccrg.hpp:10215-10219) / unrefined_cell_data (10387)
+// applied on the device by stop_refining's rebuild, located as
+// get_existing_cell (6316-6336)
+int dccrgx_particles_follow_mesh(dccrgx_grid* gp, int var_field, int record_doubles) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		particles_follow_set(g, var_field, record_doubles);
+		return 0;
+	});
+}
+
+int dccrgx_particles_adapt_stats(dccrgx_grid* gp, int var_field, uint64_t out[3]) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		const Field& f = field(g, var_field);
+		DX_REQUIRE(f.var, "not a variable-size field");
+		DX_REQUIRE(out, "null pointer");
+		for (int k = 0; k < 3; k++) out[k] = f.adapt_stats[k];
+		return 0;
+	});
+}
+
 // cells_to_send / cells_to_receive while a balance_load is in progress
 // (initialize_balance_load fills them with the migration lists, 3746-3884)
 int dccrgx_get_migration_cells(dccrgx_grid* gp, int peer, int incoming, uint64_t* ids, size_t cap, size_t* n) {

@@ -46,6 +46,16 @@ bool gol_slab_plan(Grid& g, std::vector<GolBox>& inner, std::vector<GolBox>& out
 // of K-double particle records (stats: stayed, moved, arrived, handed over, lost)
 void existing_cells_at(Grid& g, const double* xyz, size_t n, uint64_t* ids);
 void particles_step(Grid& g, int fid, int K, const double* velocity, double dt, uint64_t stats[5]);
+// particles follow the mesh through stop_refining (Field::follow_K records):
+// follow_set turns it on (K >= 3) or off (K == 0); follow_check, before the
+// mesh changes, is false when a local cell's bytes are no whole records;
+// follow_rebuild replaces var_remap in stop_refining's rebuild: the records
+// of a refined old local cell go to the children point location names on the
+// new mesh, a merged family's parent takes the removed store's records
+void particles_follow_set(Grid& g, int fid, int K);
+bool particles_follow_check(Grid& g, const Field& f);
+void particles_follow_rebuild(Grid& g, Field& f, const uint64_t* old_ids, size_t n_old_local, const DevMesh& newM,
+                              size_t new_n_slots, size_t new_n_local, hipStream_t s);
 // the active stretched geometry's coordinates on the device (x, then y, then
 // z, packed), uploaded at first use
 const double* stretched_device(Grid& g);

@@ -336,6 +336,11 @@ struct Field {
 	// cache over the inner cells, which read no remote copy, checks this one
 	uint64_t local_epoch = 0;
 	bool external = false;
+	// particles follow the mesh (particles.hip): records of follow_K doubles
+	// (0: off) go to the new children / the new parent in stop_refining;
+	// adapt_stats = {to children, to parents, lost} of the last one
+	int follow_K = 0;
+	uint64_t adapt_stats[3] = {0, 0, 0};
 	bool full_window() const { return win_off == 0 && win_len == elem; }
 };
 
@@ -608,6 +613,9 @@ struct Grid {
 	std::unordered_set<uint64_t> dont_refine_cells;    // dont_refine 2744
 	LazyIds removed_ids;  // get_removed_cells 3497 (order of Field::removed)
 	LazyIds new_cells;    // local cells created by the last stop_refining (ascending on the host)
+	// the rebuild in progress is stop_refining's: a following field's records
+	// go to the new children and the new parents (particles_follow_rebuild)
+	bool adapting = false;
 	Migration mig;
 	// the range map over the full id range of every level (one process,
 	// Morton-ordered own leaves: rebuild's "direct" mode), kept across

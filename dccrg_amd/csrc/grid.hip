@@ -591,6 +591,19 @@ void stop_refining_impl(Grid& g) {
 	const int nh = int(g.hood.size() / 3);
 	hipStream_t s = g.s_comp;
 	DX_LAPS(s);
+	// particles that follow the mesh: every local cell holds whole records, or
+	// nothing changes (the requests stay); every process learns of a refusal
+	bool following = false;
+	for (auto& f : g.fields) following = following || (f.var && f.follow_K);
+	if (following) {
+		bool ok = true;
+		for (auto& f : g.fields)
+			if (f.var && f.follow_K) ok = particles_follow_check(g, f) && ok;
+		if (g.size > 1) ok = gather_union(g, ok ? std::vector<uint64_t>{} : std::vector<uint64_t>{1}).empty();
+		DX_REQUIRE(ok, "particles follow the mesh: a cell's payload is not a multiple of 8 * record_doubles bytes");
+		for (auto& f : g.fields)
+			for (uint64_t& v : f.adapt_stats) v = 0;
+	}
 	for (auto& f : g.fields) {
 		f.removed.release();
 		f.rm_off.release();
@@ -876,7 +889,14 @@ void stop_refining_impl(Grid& g) {
 		nm.n_prefix = pos_at[1];
 	}
 	DX_LAP("sr.6_apply");
-	rebuild(g, nm);
+	g.adapting = following;
+	try {
+		rebuild(g, nm);
+	} catch (...) {
+		g.adapting = false;
+		throw;
+	}
+	g.adapting = false;
 	DX_LAP("sr.7_rebuild");
 	if (g.size == 1 && !F.empty()) {
 		g.merged_dev = std::move(dF);

@@ -8,7 +8,7 @@
 #include <numeric>
 #include <set>
 
-#include "dccrgx_internal.hpp"
+#include "dccrgx_grid.hpp"
 
 namespace dccrgx {
 
@@ -623,6 +623,13 @@ void rebuild(Grid& g, Mesh& nm) {
 		f.local_zero = false;
 		field_written(f);
 		f.external = false;  // the array moves: a pointer handed out before is void
+		if (f.var && f.follow_K && g.adapting) {
+			// stop_refining with particles following the mesh: the refined
+			// parents' records to their children, the removed children's to
+			// their parent (particles.hip)
+			particles_follow_rebuild(g, f, old_slot_ids.p, old_slot_ids.p ? old_n_local : 0, dm, g.n_slots, nl, s);
+			continue;
+		}
 		if (f.var) {  // children and new copies start empty (the reference default-constructs them)
 			var_remap(f, old_slot_ids.p, old_slot_ids.p ? old_n_local : 0, dm, g.n_slots, s);
 			continue;

@@ -713,4 +713,433 @@ void particles_step(Grid& g, int fid, int K, const double* velocity, double dt, 
 	for (int k = 0; k < 4; k++) stats[1 + k] = h[k];
 }
 
+// ---------------------------------------------------------------------------
+// Particles follow the mesh (DESIGN.md "Particles"): in stop_refining's
+// rebuild a following field's records go where the reference's user code
+// would put them from refined_cell_data (dccrg.hpp:10215-10219) and
+// unrefined_cell_data (10387): a refined parent's to the child that
+// get_existing_cell (6316-6336) names on the new mesh, the removed children's
+// to their new parent.  The passes:
+//   1. classify - a thread per old local cell: its new slot (stays), or
+//                 refined (its first child is a local cell of the new mesh),
+//                 or gone (merged into a parent: its bytes are in the removed
+//                 store); the refined ones compacted into a list;
+//   2. locate   - a wave per refined parent walks its records 64 at a time:
+//                 the child (0..7, 8: none) of each into a byte per record,
+//                 the per-child counts by ballots, the children's new sizes;
+//   3. parents  - the removed store's cells grouped by parent (children in
+//                 ascending id), a parent's new size the sum of theirs;
+//   4. a scan of the new sizes;
+//   5. scatter  - stayers cell by cell, the refined parents' records by
+//                 (child, rank of the record among the child's: ballots and
+//                 running counts), the removed children's after one another
+//                 into a fresh pool, swapped in.
+// No atomic decides a position: only the three statistics are added up.
+namespace {
+
+constexpr int kFB = 256;  // four waves, one refined parent each per pass
+
+__global__ void follow_sizes_ok_kernel(const uint64_t* __restrict__ voff, size_t n, uint64_t rec,
+                                       int32_t* __restrict__ flag) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
+		const uint64_t b = voff[i + 1] - voff[i];
+		if ((b / rec) * rec != b) *flag = 1;
+	}
+}
+
+// src: the old local cell of every new slot (-1 preset); refined: n_old + 1 flags
+__global__ void follow_classify_kernel(const MapCtx m, const DevMesh newM, const uint64_t* __restrict__ old_ids,
+                                       size_t n_old, size_t new_n_local, int32_t* __restrict__ src,
+                                       uint32_t* __restrict__ refined) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i <= n_old; i += size_t(gridDim.x) * blockDim.x) {
+		uint32_t r = 0;
+		if (i < n_old) {
+			const uint64_t id = old_ids[i];
+			const int32_t ns = dm_slot(newM, id);
+			if (ns >= 0) {
+				src[ns] = int32_t(i);
+			} else {
+				const uint64_t c0 = map_child(m, id);
+				if (c0 != id && c0 != error_cell) {
+					const int32_t cs = dm_slot(newM, c0);
+					r = cs >= 0 && size_t(cs) < new_n_local ? 1u : 0u;
+				}
+			}
+		}
+		refined[i] = r;
+	}
+}
+
+__global__ void follow_compact_kernel(const uint32_t* __restrict__ refined, const uint32_t* __restrict__ rpos,
+                                      size_t n_old, int32_t* __restrict__ plist) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n_old; i += size_t(gridDim.x) * blockDim.x)
+		if (refined[i]) plist[rpos[i]] = int32_t(i);
+}
+
+__global__ void follow_stay_sizes_kernel(const int32_t* __restrict__ src, const uint64_t* __restrict__ ooff, size_t n,
+                                         uint64_t* __restrict__ sizes) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i <= n; i += size_t(gridDim.x) * blockDim.x)
+		sizes[i] = i < n && src[i] >= 0 ? ooff[src[i] + 1] - ooff[src[i]] : 0;
+}
+
+// (pointers and counts only: the mapping, the mesh and the geometry are kernel
+// parameters of their own, see PArgs)
+struct FArgs {
+	const double* pool;          // the old pool
+	const uint64_t* ooff;        // its byte offsets per old slot
+	const uint64_t* old_ids;     // old local slots' ids
+	const int32_t* plist;        // the refined old local slots
+	size_t P;
+	int K;
+	size_t new_n_local;
+	uint8_t* child;              // per old record: its child 0..7, 8: none
+	int32_t* cslot;              // 8 per refined parent: the children's new slots
+	uint64_t* sizes;             // per new slot: bytes
+	unsigned long long* stats;   // to children, to parents, lost
+};
+
+template <class Geo>
+__global__ __launch_bounds__(kFB) void follow_locate_kernel(const MapCtx m, const DevMesh M, const Geo G,
+                                                              const FArgs a) {
+	constexpr bool kStretched = std::is_same<Geo, SGeo>::value;
+	double* s_c = nullptr;
+	bool coords_cached = false;
+	if constexpr (kStretched) {
+		__shared__ double s_coords[kCoordCache];
+		s_c = s_coords;
+		coords_cached = stage_coordinates(G, s_c);
+	}
+	// the two counts of a block are added up in LDS, one global atomic per
+	// block and count (one per child of every parent, all on one address,
+	// cost 19 ms at 262 144 parents where the whole carry now takes 0.7 ms)
+	__shared__ unsigned long long s_cnt[2];
+	if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+	__syncthreads();
+	uint32_t n_placed = 0, n_lost = 0;
+	const uint32_t lane = threadIdx.x & 63u;
+	const size_t waves = size_t(gridDim.x) * (kFB >> 6);
+	const uint64_t rec = uint64_t(a.K) * sizeof(double);
+	for (size_t j = blockIdx.x * size_t(kFB >> 6) + (threadIdx.x >> 6); j < a.P; j += waves) {
+		const size_t os = size_t(a.plist[j]);
+		uint64_t ch[8];
+		map_all_children(m, a.old_ids[os], ch);
+		const size_t first = size_t(a.ooff[os] / rec), n = size_t((a.ooff[os + 1] - a.ooff[os]) / rec);
+		uint32_t mine = 0;  // lane k < 8: records of child k; lane 8: of none
+		for (size_t r0 = 0; r0 < n; r0 += 64) {
+			const bool valid = r0 + lane < n;
+			uint32_t c = 9;
+			if (valid) {
+				const double* r = a.pool + (first + r0 + lane) * size_t(a.K);
+				const double x[3] = {r[0], r[1], r[2]};
+				uint64_t leaf;
+				if constexpr (kStretched)
+					leaf = coords_cached ? stretched_cell_at(m, M, G, s_c, x) : stretched_cell_at(m, M, G, G.c, x);
+				else
+					leaf = existing_cell_at(m, M, G, x);
+				c = 8;
+#pragma unroll
+				for (int k = 0; k < 8; k++)
+					if (leaf == ch[k] && leaf != error_cell) c = uint32_t(k);
+				a.child[first + r0 + lane] = uint8_t(c);
+			}
+#pragma unroll
+			for (uint32_t k = 0; k < 9; k++) {
+				const unsigned long long b = __ballot(c == k);
+				if (lane == k) mine += uint32_t(__popcll(b));
+			}
+		}
+		if (lane < 8) {
+			const int32_t cs = dm_slot(M, ch[lane]);
+			// (the classify pass saw the first child local; every child of a
+			// refined local cell is created on its process)
+			const bool ok = cs >= 0 && size_t(cs) < a.new_n_local;
+			a.cslot[8 * j + lane] = ok ? cs : -1;
+			if (ok) {
+				a.sizes[cs] = uint64_t(mine) * rec;
+				n_placed += mine;
+			} else {
+				n_lost += mine;
+			}
+		} else if (lane == 8) {
+			n_lost += mine;
+		}
+	}
+	if (n_placed) atomicAdd(&s_cnt[0], (unsigned long long)n_placed);
+	if (n_lost) atomicAdd(&s_cnt[1], (unsigned long long)n_lost);
+	__syncthreads();
+	if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&a.stats[threadIdx.x == 0 ? 0 : 2], s_cnt[threadIdx.x]);
+}
+
+// a refined parent's records into its children, each child's in the parent's order
+__global__ __launch_bounds__(kFB) void follow_scatter_children_kernel(const FArgs a, const uint64_t* __restrict__ noff,
+                                                                        double* __restrict__ out) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const size_t waves = size_t(gridDim.x) * (kFB >> 6);
+	const uint64_t rec = uint64_t(a.K) * sizeof(double);
+	const unsigned long long below = (1ull << lane) - 1ull;
+	for (size_t j = blockIdx.x * size_t(kFB >> 6) + (threadIdx.x >> 6); j < a.P; j += waves) {
+		const size_t os = size_t(a.plist[j]);
+		const size_t first = size_t(a.ooff[os] / rec), n = size_t((a.ooff[os + 1] - a.ooff[os]) / rec);
+		// per child (the same in every lane, indexed by unrolled constants
+		// only): the record index of its first record in the new pool (~0: no
+		// slot) and its records placed so far
+		uint64_t start[8];
+		uint32_t base[8];
+#pragma unroll
+		for (int k = 0; k < 8; k++) {
+			const int32_t sl = a.cslot[8 * j + k];
+			start[k] = sl >= 0 ? noff[sl] / rec : ~uint64_t(0);
+			base[k] = 0;
+		}
+		for (size_t r0 = 0; r0 < n; r0 += 64) {
+			const bool valid = r0 + lane < n;
+			const uint32_t c = valid ? a.child[first + r0 + lane] : 9u;
+			uint64_t q = 0;
+			bool place = false;
+#pragma unroll
+			for (uint32_t k = 0; k < 8; k++) {
+				const unsigned long long b = __ballot(c == k);
+				if (c == k && start[k] != ~uint64_t(0)) {
+					q = start[k] + base[k] + uint32_t(__popcll(b & below));
+					place = true;
+				}
+				base[k] += uint32_t(__popcll(b));
+			}
+			if (place) copy_record(out + q * size_t(a.K), a.pool + (first + r0 + lane) * size_t(a.K), a.K);
+		}
+	}
+}
+
+// a wave per new slot that keeps its old cell's records
+__global__ void follow_copy_stays_kernel(const double* __restrict__ pool, const uint64_t* __restrict__ ooff,
+                                         const int32_t* __restrict__ src, double* __restrict__ out,
+                                         const uint64_t* __restrict__ noff, size_t n) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const size_t waves = size_t(gridDim.x) * (blockDim.x >> 6);
+	for (size_t i = blockIdx.x * size_t(blockDim.x >> 6) + (threadIdx.x >> 6); i < n; i += waves) {
+		if (src[i] < 0) continue;
+		const double* from = pool + ooff[src[i]] / 8;
+		double* to = out + noff[i] / 8;
+		const uint64_t len = (noff[i + 1] - noff[i]) / 8;
+		for (uint64_t k = lane; k < len; k += 64) to[k] = from[k];
+	}
+}
+
+__global__ void removed_parent_ids_kernel(const MapCtx m, const uint64_t* __restrict__ rm, size_t n,
+                                          uint64_t* __restrict__ par) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x)
+		par[i] = map_parent(m, rm[i]);
+}
+
+// the removed store's cell i belongs to row `lo` of the sorted parents, at
+// its place among the eight children (map_all_children order = ascending id)
+__global__ void follow_rows_kernel(const MapCtx m, const uint64_t* __restrict__ rm, size_t n,
+                                   const uint64_t* __restrict__ parents, size_t np, int32_t* __restrict__ cidx) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
+		uint64_t x, y, z;
+		const int l = map_indices(m, rm[i], x, y, z);
+		if (l <= 0) continue;
+		const uint64_t p = map_parent(m, rm[i]);
+		const size_t lo = upper_bound_idx<uint64_t>(parents, 0, np, p - 1);  // first parents[lo] >= p
+		if (lo >= np || parents[lo] != p) continue;
+		const uint64_t o = uint64_t(1) << (m.R - l);  // the child's length in indices
+		const int k = int((x / o) & 1u) | int(((y / o) & 1u) << 1) | int(((z / o) & 1u) << 2);
+		cidx[8 * lo + size_t(k)] = int32_t(i);
+	}
+}
+
+__global__ void follow_parent_sizes_kernel(const int32_t* __restrict__ cidx, const int32_t* __restrict__ pslot,
+                                           size_t np, size_t new_n_local, const uint64_t* __restrict__ rm_off,
+                                           uint64_t rec, uint64_t* __restrict__ sizes,
+                                           unsigned long long* __restrict__ stats) {
+	__shared__ unsigned long long s_cnt;
+	if (threadIdx.x == 0) s_cnt = 0;
+	__syncthreads();
+	unsigned long long n_records = 0;
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < np; i += size_t(gridDim.x) * blockDim.x) {
+		if (pslot[i] < 0 || size_t(pslot[i]) >= new_n_local) continue;
+		uint64_t b = 0;
+		for (int k = 0; k < 8; k++) {
+			const int32_t c = cidx[8 * i + k];
+			if (c >= 0) b += rm_off[c + 1] - rm_off[c];
+		}
+		sizes[pslot[i]] = b;
+		n_records += b / rec;
+	}
+	if (n_records) atomicAdd(&s_cnt, n_records);
+	__syncthreads();
+	if (threadIdx.x == 0 && s_cnt) atomicAdd(&stats[1], s_cnt);
+}
+
+// a wave per (parent, child): the child's removed bytes after its smaller siblings'
+__global__ void follow_copy_parents_kernel(const int32_t* __restrict__ cidx, const int32_t* __restrict__ pslot,
+                                           size_t np, size_t new_n_local, const uint64_t* __restrict__ rm_off,
+                                           const double* __restrict__ removed, const uint64_t* __restrict__ noff,
+                                           double* __restrict__ out) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const size_t waves = size_t(gridDim.x) * (blockDim.x >> 6);
+	for (size_t w = blockIdx.x * size_t(blockDim.x >> 6) + (threadIdx.x >> 6); w < 8 * np; w += waves) {
+		const size_t i = w / 8;
+		const int k = int(w % 8);
+		const int32_t c = cidx[w];
+		if (c < 0 || pslot[i] < 0 || size_t(pslot[i]) >= new_n_local) continue;
+		uint64_t before = 0;
+		for (int q = 0; q < k; q++) {
+			const int32_t e = cidx[8 * i + q];
+			if (e >= 0) before += rm_off[e + 1] - rm_off[e];
+		}
+		const double* from = removed + rm_off[c] / 8;
+		double* to = out + (noff[pslot[i]] + before) / 8;
+		const uint64_t len = (rm_off[c + 1] - rm_off[c]) / 8;
+		for (uint64_t t = lane; t < len; t += 64) to[t] = from[t];
+	}
+}
+
+unsigned follow_wave_grid(size_t n) { return grid_for(n, kFB >> 6, 8192); }
+
+}  // namespace
+
+void particles_follow_set(Grid& g, int fid, int K) {
+	Field& f = field(g, fid);
+	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	DX_REQUIRE(K == 0 || K >= 3, "a particle record has at least 3 doubles (the position)");
+	f.follow_K = K;
+	for (uint64_t& v : f.adapt_stats) v = 0;
+}
+
+bool particles_follow_check(Grid& g, const Field& f) {
+	require_geometry(g);
+	if (!g.n_local || !f.voff.p) return true;
+	hipStream_t s = g.s_comp;
+	DBuf<int32_t> flag;
+	flag.alloc(1);
+	HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, s));
+	follow_sizes_ok_kernel<<<grid_for(g.n_local, 256), 256, 0, s>>>(f.voff.p, g.n_local,
+	                                                               uint64_t(f.follow_K) * sizeof(double), flag.p);
+	HIP_CHECK(hipGetLastError());
+	int32_t bad = 0;
+	d2h_small(&bad, flag.p, 4, s);
+	return !bad;
+}
+
+void particles_follow_rebuild(Grid& g, Field& f, const uint64_t* old_ids, size_t n_old, const DevMesh& newM,
+                              size_t ns, size_t nl, hipStream_t s) {
+	const int K = f.follow_K;
+	const uint64_t rec = uint64_t(K) * sizeof(double);
+	const bool had = n_old && f.voff.p;
+	DBuf<unsigned long long> dstats;
+	dstats.alloc(3);
+	HIP_CHECK(hipMemsetAsync(dstats.p, 0, 3 * sizeof(unsigned long long), s));
+
+	// 1. classify
+	DBuf<int32_t> src, plist;
+	DBuf<uint32_t> refined, rpos;
+	src.alloc(ns + 1);
+	k_fill_i32(src.p, ns + 1, -1, s);
+	size_t P = 0;
+	if (had) {
+		refined.alloc(n_old + 1);
+		rpos.alloc(n_old + 1);
+		follow_classify_kernel<<<grid_for(n_old + 1, 256), 256, 0, s>>>(g.m, newM, old_ids, n_old, nl, src.p, refined.p);
+		HIP_CHECK(hipGetLastError());
+		P = scan_exclusive_u32(refined.p, rpos.p, n_old, s);
+	}
+	DBuf<uint64_t> sizes, noff;
+	sizes.alloc(ns + 1);
+	noff.alloc(ns + 1);
+	if (had) {
+		follow_stay_sizes_kernel<<<grid_for(ns + 1, 256), 256, 0, s>>>(src.p, f.voff.p, ns, sizes.p);
+		HIP_CHECK(hipGetLastError());
+	} else {
+		HIP_CHECK(hipMemsetAsync(sizes.p, 0, (ns + 1) * 8, s));
+	}
+
+	// 2. locate the refined parents' records on the new mesh
+	FArgs a{};
+	DBuf<uint8_t> child;
+	DBuf<int32_t> cslot;
+	if (P) {
+		const uint64_t total = var_total(f, n_old, s);  // the old pool's local part ends at voff[n_old]
+		plist.alloc(P);
+		follow_compact_kernel<<<grid_for(n_old, 256), 256, 0, s>>>(refined.p, rpos.p, n_old, plist.p);
+		HIP_CHECK(hipGetLastError());
+		child.alloc(size_t(total / rec) + 1);
+		cslot.alloc(8 * P);
+		a.pool = reinterpret_cast<const double*>(f.data.p);
+		a.ooff = f.voff.p;
+		a.old_ids = old_ids;
+		a.plist = plist.p;
+		a.P = P;
+		a.K = K;
+		a.new_n_local = nl;
+		a.child = child.p;
+		a.cslot = cslot.p;
+		a.sizes = sizes.p;
+		a.stats = dstats.p;
+		if (total) {
+			if (g.str.active)
+				follow_locate_kernel<SGeo><<<follow_wave_grid(P), kFB, 0, s>>>(g.m, newM, make_sgeo(g), a);
+			else
+				follow_locate_kernel<PGeo><<<follow_wave_grid(P), kFB, 0, s>>>(g.m, newM, make_geo(g), a);
+			HIP_CHECK(hipGetLastError());
+		} else {
+			P = 0;  // nothing to place: the children keep size 0
+		}
+	}
+
+	// 3. the merged families' parents take the removed store's records
+	const size_t n_rm = f.rm_off.p ? g.removed_ids.size() : 0;
+	DBuf<uint64_t> up, par;
+	DBuf<int32_t> cidx, pslot, err;
+	size_t np = 0;
+	const uint64_t* rm_dev = nullptr;
+	if (n_rm) {
+		rm_dev = g.removed_ids.dev();
+		if (!rm_dev) {
+			upload(up, g.removed_ids.host(s), s);
+			rm_dev = up.p;
+		}
+		par.alloc(n_rm);
+		removed_parent_ids_kernel<<<grid_for(n_rm, 256), 256, 0, s>>>(g.m, rm_dev, n_rm, par.p);
+		HIP_CHECK(hipGetLastError());
+		np = sort_unique_u64(par.p, n_rm, s, map_id_bits(g.m));
+		cidx.alloc(8 * np);
+		pslot.alloc(np);
+		err.alloc(1);
+		HIP_CHECK(hipMemsetAsync(cidx.p, 0xff, 8 * np * sizeof(int32_t), s));
+		HIP_CHECK(hipMemsetAsync(err.p, 0, 4, s));
+		follow_rows_kernel<<<grid_for(n_rm, 256), 256, 0, s>>>(g.m, rm_dev, n_rm, par.p, np, cidx.p);
+		HIP_CHECK(hipGetLastError());
+		k_lookup_slots(par.p, np, newM, pslot.p, err.p, s);  // (a parent without a slot: -1, skipped)
+		follow_parent_sizes_kernel<<<grid_for(np, 256), 256, 0, s>>>(cidx.p, pslot.p, np, nl, f.rm_off.p, rec, sizes.p,
+		                                                             dstats.p);
+		HIP_CHECK(hipGetLastError());
+	}
+
+	// 4. new offsets, 5. scatter into a fresh pool
+	const uint64_t total = scan_exclusive_u64(sizes.p, noff.p, ns, s);
+	DBuf<uint8_t> nd;
+	nd.alloc(total + 1);
+	double* out = reinterpret_cast<double*>(nd.p);
+	if (total && had && f.data.p) {
+		follow_copy_stays_kernel<<<follow_wave_grid(ns), kFB, 0, s>>>(reinterpret_cast<const double*>(f.data.p),
+		                                                              f.voff.p, src.p, out, noff.p, ns);
+		HIP_CHECK(hipGetLastError());
+	}
+	if (total && P) {
+		follow_scatter_children_kernel<<<follow_wave_grid(P), kFB, 0, s>>>(a, noff.p, out);
+		HIP_CHECK(hipGetLastError());
+	}
+	if (total && np && f.removed.p) {
+		follow_copy_parents_kernel<<<follow_wave_grid(8 * np), kFB, 0, s>>>(
+		    cidx.p, pslot.p, np, nl, f.rm_off.p, reinterpret_cast<const double*>(f.removed.p), noff.p, out);
+		HIP_CHECK(hipGetLastError());
+	}
+	unsigned long long h[3] = {0, 0, 0};
+	d2h_small(h, dstats.p, sizeof(h), s);  // drains s: the temporaries end here
+	f.data.swap(nd);
+	f.voff.swap(noff);
+	for (int k = 0; k < 3; k++) f.adapt_stats[k] = h[k];
+}
+
 }  // namespace dccrgx

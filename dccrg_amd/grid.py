@@ -907,6 +907,20 @@ class Dccrg:
         check(lib().dccrgx_particles_step(self.h, field.id, int(record_doubles), v, float(dt), st))
         return dict(zip(("stayed", "moved", "arrived", "handed_over", "lost"), (int(x) for x in st)))
 
+    def particles_follow_mesh(self, field, record_doubles=3):
+        """The records of the variable float64 field `field` follow the mesh
+        in every stop_refining (advection_adapt's included): a refined
+        parent's go to the children their positions lie in, a merged family's
+        parent takes its removed children's (ascending child id).
+        record_doubles=0 turns it off again (the default: new cells empty)."""
+        check(lib().dccrgx_particles_follow_mesh(self.h, field.id, int(record_doubles)))
+
+    def particles_adapt_stats(self, field):
+        """This process's counts of the last stop_refining for a following field."""
+        st = (C.c_uint64 * 3)()
+        check(lib().dccrgx_particles_adapt_stats(self.h, field.id, st))
+        return dict(zip(("to_children", "to_parents", "lost"), (int(x) for x in st)))
+
     # ---- built-in sweeps ------------------------------------------------------------
     def gol_step(self, state: Field, region="all"):
         check(lib().dccrgx_gol_step(self.h, state.id, REGION[region]))

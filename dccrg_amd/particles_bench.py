@@ -9,7 +9,12 @@ the same pool in the same run (the library's copy-once yardstick).
 
 --stretched measures the same grid under a Stretched_Cartesian_Geometry of
 unequal cells (dccrgx_set_stretched_geometry) next to the Cartesian step, and
-records the parent commit's Cartesian lines given with --parent."""
+records the parent commit's Cartesian lines given with --parent.
+
+--adapt measures what it costs that the particles follow the mesh
+(Dccrg.particles_follow_mesh): on the same 128^3 base with R = 1 a z-slab of
+one eighth of the cells is refined and merged again, and the two stop_refining
+calls are timed with follow on and off, beside one re-lay of the pool."""
 from __future__ import annotations
 
 import argparse
@@ -128,14 +133,21 @@ def main(argv=None):
     p.add_argument("--stretched", action="store_true",
                    help="the same grid under a stretched geometry of unequal cells, next to the Cartesian step "
                         "(--repeats of each, alternating); writes profiles/particles_bench_stretched.json unless --out")
+    p.add_argument("--adapt", action="store_true",
+                   help="particles following the mesh: a z-slab of a base^3, R = 1 grid refined and merged again, "
+                        "stop_refining with follow on against follow off (--repeats of each, alternating) and "
+                        "against one re-lay of the pool; writes profiles/particles_bench_adapt.json unless --out")
     p.add_argument("--repeats", type=int, default=3)
     p.add_argument("--parent", default=None,
                    help="with --stretched: files of lines the parent commit's particles_bench printed in the same "
-                        "machine visit (comma-separated), recorded as the parent's Cartesian step")
+                        "machine visit (comma-separated), recorded as the parent's Cartesian step; with --adapt: "
+                        "files of measure_adapt(follow=False) results taken with the parent commit's library")
     a = p.parse_args(argv)
 
     import torch  # noqa: F401  (one HIP runtime for the process)
 
+    if a.adapt:
+        return main_adapt(a)
     if a.stretched:
         return main_stretched(a)
     r = measure(a)
@@ -193,6 +205,114 @@ def main_stretched(a):
     print(txt, flush=True)
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                 "particles_bench_stretched.json")
+    with open(out, "w") as f:
+        f.write(txt + "\n")
+
+
+def measure_adapt(a, follow):
+    """One refinement and one unrefinement of a z-slab (one eighth of the
+    cells) of a fresh base^3 periodic grid with R = 1 and ppc particles per
+    cell: the times of the two stop_refining calls, with the particle field
+    following the mesh or not (then the slab's particles are dropped, as the
+    default is), and one re-lay of the full pool before them."""
+    import dccrg_amd
+    from dccrg_amd._lib import check, lib
+
+    n = a.base
+    g = dccrg_amd.Dccrg(0, 1, 0).set_initial_length((n, n, n)).set_neighborhood_length(1)
+    g.set_maximum_refinement_level(1).set_periodic(True, True, True).initialize()
+    fld = g.add_variable_field("particles", np.float64, True)
+    if follow:
+        g.particles_follow_mesh(fld, K)
+    ids = g.slot_ids()[: g.n_local]
+    nc = ids.size
+    k = (ids - np.uint64(1)).astype(np.int64)
+    ix = np.stack([k % n, (k // n) % n, k // (n * n)], axis=1)
+    rng = np.random.default_rng(1)
+    pos = (ix.astype(np.float64)[:, None, :] + rng.random((nc, a.ppc, 3))).reshape(-1)
+    fld.resize(np.full(nc, a.ppc * K, np.uint64))
+    check(lib().dccrgx_variable_field_upload(g.h, fld.id, 0, nc, pos.ctypes.data_as(C.c_void_p), pos.nbytes))
+    del pos
+    cur = fld.sizes(0, nc) // np.uint64(8)
+    g.synchronize()
+    relay = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        fld.resize(cur)
+        g.synchronize()
+        relay.append((time.perf_counter() - t0) * 1e3)
+
+    def timed_stop_refining():
+        g.synchronize()
+        t0 = time.perf_counter()
+        g.stop_refining()
+        g.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    slab = ids[ix[:, 2] < max(n // 8, 1)]
+    for c in slab:
+        g.refine_completely(int(c))
+    refine_ms = timed_stop_refining()
+    st_refine = g.particles_adapt_stats(fld) if follow else None
+    cells_refined = int(g.n_local)
+    for c in g.mapping_batch(slab)["child"]:
+        g.unrefine_completely(int(c))
+    unrefine_ms = timed_stop_refining()
+    st_unrefine = g.particles_adapt_stats(fld) if follow else None
+    left = int(fld.sizes(0, g.n_local).sum()) // (8 * K)
+    assert g.n_local == nc, (g.n_local, nc)
+    if follow:
+        moved = slab.size * a.ppc
+        assert st_refine == dict(to_children=moved, to_parents=0, lost=0), st_refine
+        assert st_unrefine == dict(to_children=0, to_parents=moved, lost=0), st_unrefine
+        assert left == nc * a.ppc, left
+    g.close()
+    return dict(follow=bool(follow), refine_ms=refine_ms, unrefine_ms=unrefine_ms, relay_ms=min(relay),
+                cells=int(nc), cells_refined=cells_refined, refined_parents=int(slab.size),
+                particles=int(nc * a.ppc), particles_left=left)
+
+
+def main_adapt(a):
+    """Follow on and off on this tree, alternating, each on a fresh grid; the
+    medians, every run, and the parent commit's follow-off runs when given."""
+    runs = {"off": [], "on": []}
+    for _ in range(max(a.repeats, 1)):
+        runs["off"].append(measure_adapt(a, False))
+        runs["on"].append(measure_adapt(a, True))
+    med = {k: {w: float(np.median([r[w] for r in v])) for w in ("refine_ms", "unrefine_ms", "relay_ms")}
+           for k, v in runs.items()}
+    relay = float(np.median([r["relay_ms"] for v in runs.values() for r in v]))
+    cost = {w: med["on"][w] - med["off"][w] for w in ("refine_ms", "unrefine_ms")}
+    r0 = runs["on"][0]
+    line = {"metric": "particles_follow_mesh", "value": cost["refine_ms"], "unit": "ms", "n_gpus": 1,
+            "higher_is_better": False, "dtype": "fp64",
+            "config": {"workload": f"{a.base}^3 periodic, R = 1, neighborhood 1, {a.ppc} particles per cell, K = {K}; "
+                                   "a z-slab of one eighth of the cells refined by one stop_refining, the same "
+                                   "families merged by the next; a fresh grid per run, follow off and on alternating",
+                       "cells": r0["cells"], "refined_parents": r0["refined_parents"], "particles": r0["particles"],
+                       "particles_carried": r0["refined_parents"] * a.ppc, "repeats": a.repeats},
+            "follow_on": {**med["on"], "runs": runs["on"]}, "follow_off": {**med["off"], "runs": runs["off"]},
+            "carry_cost_ms": {"refine": cost["refine_ms"], "unrefine": cost["unrefine_ms"],
+                              "what": "median stop_refining with follow on minus with follow off"},
+            "relay": {"what": "VariableField.resize of the full pool, sizes unchanged (copy once)", "ms": relay,
+                      "refine_cost_over_relay": cost["refine_ms"] / relay,
+                      "unrefine_cost_over_relay": cost["unrefine_ms"] / relay}}
+    if a.parent:
+        pr = []
+        for path in a.parent.split(","):
+            with open(path) as f:
+                pr += [json.loads(ln) for ln in f if ln.strip()]
+        line["parent_follow_off"] = {
+            "what": "the parent commit's stop_refining of the same scenario (no follow members), same machine visit",
+            "refine_ms": float(np.median([r["refine_ms"] for r in pr])),
+            "unrefine_ms": float(np.median([r["unrefine_ms"] for r in pr])), "runs": pr}
+        for w in ("refine_ms", "unrefine_ms"):
+            v = [r[w] for r in pr]
+            line["parent_follow_off"][w + "_spread"] = [min(v), max(v)]
+    txt = json.dumps(line)
+    print(txt, flush=True)
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "particles_bench_adapt.json")
     with open(out, "w") as f:
         f.write(txt + "\n")
 

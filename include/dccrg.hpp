@@ -1219,6 +1219,19 @@ public:
 		                                    st.data()));
 		return st;
 	}
+	// the records follow the mesh in every stop_refining: what user code does
+	// from refined_cell_data / unrefined_cell_data, on the device (a refined
+	// parent's records to the child at their position, the removed children's
+	// to their new parent); record_doubles 0 turns it off again
+	void particles_follow_mesh(const Device_Variable_Field<double>& particles, const int record_doubles = 3) {
+		detail::check(dccrgx_particles_follow_mesh(g_, particles.id(), record_doubles));
+	}
+	// {to children, to parents, lost} of this process in the last stop_refining
+	std::array<uint64_t, 3> particles_adapt_stats(const Device_Variable_Field<double>& particles) const {
+		std::array<uint64_t, 3> st{{0, 0, 0}};
+		detail::check(dccrgx_particles_adapt_stats(g_, particles.id(), st.data()));
+		return st;
+	}
 
 	// advection (tests/advection): fields density, vx, vy, vz, lx, ly, lz
 	using Advection_Fields = std::array<Device_Field<double>, 7>;

@@ -442,6 +442,28 @@ int dccrgx_get_existing_cells_at(dccrgx_grid* g, const double* xyz, size_t n, ui
  * velocity NULL with K < 6, a stretched geometry block. */
 int dccrgx_particles_step(dccrgx_grid* g, int var_field, int record_doubles, const double* velocity, double dt,
                           uint64_t* stats);
+/* Particles follow the mesh.  The reference hands a refined parent's data to
+ * the user in refined_cell_data (dccrg.hpp:10215-10219) and the removed
+ * children's in unrefined_cell_data (10387) and leaves the new cells
+ * default-constructed; with this on (record_doubles = K >= 3, 0 turns it off
+ * again; off by default) every dccrgx_stop_refining, the one inside
+ * dccrgx_advection_adapt included, moves the field's records itself, on the
+ * device: a refined local parent's record goes to the leaf of the new mesh
+ * that get_existing_cell (6316-6336; the step's point location, Cartesian or
+ * stretched) names for its stored position, which is not rewritten; each
+ * child holds its records in the parent's order; a record whose leaf is not
+ * one of the parent's eight children leaves the lists and is counted lost.
+ * The new parent of a merged family receives the removed children's records,
+ * ascending child id, each child's in their own order; the removed store
+ * (dccrgx_removed_variable_field_download) answers as before.  Cells that
+ * stay keep their records, remote copies start empty.  DCCRGX_EINVAL here: a
+ * fixed-size field, K of 1 or 2.  DCCRGX_EINVAL from the stop_refining, the
+ * mesh and the refine / unrefine requests unchanged: a local cell whose bytes
+ * are no multiple of 8 K, a stretched geometry block without coordinates. */
+int dccrgx_particles_follow_mesh(dccrgx_grid* g, int var_field, int record_doubles);
+/* out = {records moved to children, records moved to parents, lost} of this
+ * process in the last dccrgx_stop_refining */
+int dccrgx_particles_adapt_stats(dccrgx_grid* g, int var_field, uint64_t out[3]);
 
 /* set_send_single_cells 6677 / get_send_single_cells 6684: one message per
  * cell (tag = position + 1) instead of one per process.  On, the remote
