@@ -201,7 +201,11 @@ static void po_cache(Grid& g, int rhs, int sol, const uint64_t* solve, size_t ns
 	P.ell.alloc(6 * nl + 6);
 	P.fine.alloc(g.face_fine.n);
 	const PoArrays a = po_arrays(g);
-	k_po_cache(g.m, g.l0, g.slot_ids.p, cls.p, g.face_ell.p, g.face_fine.p, nl, P.ell.p, P.fine.p, type, a, s);
+	// the lengths of the geometry as it is now: Cartesian l0, or the active
+	// stretched geometry's coordinates (a remote copy's length comes from its
+	// id like a local cell's); the factors stay until the next cache pass
+	k_po_cache(g.m, g.l0, stretched_view(g), g.slot_ids.p, cls.p, g.face_ell.p, g.face_fine.p, nl, P.ell.p, P.fine.p,
+	           type, a, s);
 	HIP_CHECK(hipStreamSynchronize(s));
 	std::vector<int> geo{P.sf};  // GEOMETRY (969-970)
 	for (int k = 0; k < 6; k++) geo.push_back(P.f[k]);
@@ -2885,7 +2889,9 @@ int dccrgx_advection_commit(dccrgx_grid* gp, int df) {
 // tests/advection/initialize.hpp:36-82 + Cartesian_Geometry get_center /
 // get_length (dccrg_cartesian_geometry.hpp:282-362), evaluated on the host
 // with the reference's expression order so the initial state is bitwise the
-// reference's.
+// reference's.  With an active stretched geometry the center and the length
+// are Stretched_Cartesian_Geometry's (initialize.hpp:45-46 take them from the
+// grid's geometry, whichever it is).
 int dccrgx_advection_initialize(dccrgx_grid* gp, const int fids[7]) {
 	return guard([&] {
 		GRID_OR_FAIL(gp);
@@ -2896,6 +2902,9 @@ int dccrgx_advection_initialize(dccrgx_grid* gp, const int fids[7]) {
 		const size_t n = g.n_slots;
 		for (int k = 0; k < 7; k++) g.adv_fids[k] = fids[k];
 		g.adv_fids_valid = true;
+		const bool stretched = g.str.active;
+		for (int d = 0; d < 3 && stretched; d++)
+			DX_REQUIRE(g.str.c[d].size() == g.len[d] + 1, "the grid's length changed after set_stretched_geometry");
 		std::vector<double> a[7];
 		for (auto& v : a) v.resize(n);
 		for (size_t i = 0; i < n; i++) {
@@ -2903,9 +2912,19 @@ int dccrgx_advection_initialize(dccrgx_grid* gp, const int fids[7]) {
 			const int lvl = map_indices(g.m, ids[i], ind[0], ind[1], ind[2]);
 			const double sf = 1.0 / double(uint64_t(1) << lvl);
 			double L[3], c[3];
-			for (int d = 0; d < 3; d++) L[d] = g.l0[d] * sf;
-			for (int d = 0; d < 3; d++)
-				c[d] = g.start[d] + double(ind[d]) * g.l0[d] / double(uint64_t(1) << g.R) + L[d] / 2;
+			if (stretched) {  // dccrgx_geometry_batch's expressions
+				for (int d = 0; d < 3; d++) {
+					const std::vector<double>& x = g.str.c[d];
+					const uint64_t l0i = uint64_t(1) << g.R, i0 = ind[d] / l0i;
+					L[d] = (x[i0 + 1] - x[i0]) / double(uint64_t(1) << lvl);
+					const double length_of_index = (x[i0 + 1] - x[i0]) / double(l0i);
+					c[d] = x[i0] + length_of_index * double(ind[d] - i0 * l0i) + L[d] / 2;
+				}
+			} else {
+				for (int d = 0; d < 3; d++) L[d] = g.l0[d] * sf;
+				for (int d = 0; d < 3; d++)
+					c[d] = g.start[d] + double(ind[d]) * g.l0[d] / double(uint64_t(1) << g.R) + L[d] / 2;
+			}
 			const double radius = 0.15;
 			const double hr = std::min(std::sqrt(std::pow(c[0] - 0.25, 2.0) + std::pow(c[1] - 0.5, 2.0)), radius) / radius;
 			a[0][i] = 0.25 * (1 + std::cos(M_PI * hr));
@@ -3193,7 +3212,7 @@ int dccrgx_advection_adapt(dccrgx_grid* gp, const int fids[7], uint64_t out[2]) 
 		DX_LAP("adapt.2_parents");
 		// the reset pass also leaves the next time step's block minima
 		g.dt_part.reserve(kDtPartials);
-		const size_t nb = k_adv_reset(g.m, g.slot_ids.p, g.n_local, g.start, g.l0, f, s, g.dt_part.p);
+		const size_t nb = k_adv_reset(g.m, g.slot_ids.p, g.n_local, g.start, g.l0, stretched_view(g), f, s, g.dt_part.p);
 		dt_cache_set(g, fids, nb);
 		HIP_CHECK(hipStreamSynchronize(s));
 		DX_LAP("adapt.3_reset");

@@ -59,6 +59,9 @@ void particles_follow_rebuild(Grid& g, Field& f, const uint64_t* old_ids, size_t
 // the active stretched geometry's coordinates on the device (x, then y, then
 // z, packed), uploaded at first use
 const double* stretched_device(Grid& g);
+// the same with each dimension's offset, for the Poisson cache pass and the
+// advection reset pass (Cartesian grid: c == nullptr, nothing uploaded)
+StretchedView stretched_view(Grid& g);
 // geometry.hip: the fp64 center and / or length of every slot's cell into
 // fixed-size fp64 fields (-1: none), Cartesian or stretched
 void geometry_fill(Grid& g, const int center_fields[3], const int length_fields[3]);

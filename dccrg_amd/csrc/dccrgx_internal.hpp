@@ -351,6 +351,14 @@ inline void field_written(Field& f) {
 // a write of the field's remote copies only (halo receives)
 inline void field_halo_written(Field& f) { f.epoch++; }
 
+// the active stretched geometry as the built-in solvers' kernels take it: the
+// packed device coordinates (stretched_device) and each dimension's offset
+// into them; c == nullptr: the grid is Cartesian
+struct StretchedView {
+	const double* c = nullptr;
+	uint32_t off[3] = {0, 0, 0};
+};
+
 // ---- Poisson BiCG (tests/poisson/poisson_solve.hpp) ------------------------
 // device pointers of one solve: user fields rhs / solution, the solver's own
 // per-slot fields and the filtered face table (see poisson_kernels.hip)
@@ -1158,8 +1166,9 @@ void k_adv_parent_density(double* rho, const int32_t* parent_slot, const int32_t
 // (dt_partial: when given, the block minima of the time-step bound of the
 // values written, as k_adv_dt computes them; returns their count)
 constexpr unsigned kDtPartials = 2048;  // block minima a reset pass leaves at most
+// (G.c given: centers and lengths of the stretched geometry instead of start / l0's)
 size_t k_adv_reset(const MapCtx& m, const uint64_t* slot_ids, size_t n, const double start[3], const double l0[3],
-                   double* const f[7], hipStream_t s, double* dt_partial = nullptr);
+                   const StretchedView& G, double* const f[7], hipStream_t s, double* dt_partial = nullptr);
 void k_time_begin(Grid& g);
 void k_time_end(Grid& g);
 
@@ -1201,9 +1210,10 @@ void k_gol_amr(int phase, GolAmrTables& T, size_t n_slots, size_t n_local, uint3
 // --- launchers implemented in poisson_kernels.hip ---------------------------
 unsigned k_po_blocks(size_t n);  // blocks (= partials) of a phase launch over n slots
 void k_po_transpose(const PoArrays& a, size_t n, double* ft, hipStream_t s);
-void k_po_cache(const MapCtx& m, const double l0[3], const uint64_t* slot_ids, const int32_t* cls,
-                const int32_t* face_ell, const int32_t* face_fine, size_t n, int32_t* po_ell, int32_t* po_fine,
-                int32_t* type, const PoArrays& a, hipStream_t s);
+// (G.c given: the lengths of the stretched geometry instead of l0's)
+void k_po_cache(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
+                const int32_t* cls, const int32_t* face_ell, const int32_t* face_fine, size_t n, int32_t* po_ell,
+                int32_t* po_fine, int32_t* type, const PoArrays& a, hipStream_t s);
 void k_po_phase(int phase, const PoArrays& a, size_t n, const PoParams& prm, const PoScalars* st, double* part,
                 hipStream_t s);
 void k_po_reduce(int k, const double* part, unsigned nb, double* red, PoScalars* st, const PoParams& prm, int stage,

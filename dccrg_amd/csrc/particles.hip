@@ -529,6 +529,18 @@ const double* stretched_device(Grid& g) {
 	return T.dev.p;
 }
 
+StretchedView stretched_view(Grid& g) {
+	StretchedView V;
+	if (!g.str.active) return V;
+	V.c = stretched_device(g);
+	uint32_t at = 0;
+	for (int d = 0; d < 3; d++) {
+		V.off[d] = at;
+		at += uint32_t(g.str.c[d].size());
+	}
+	return V;
+}
+
 void existing_cells_at(Grid& g, const double* xyz, size_t n, uint64_t* ids) {
 	require_geometry(g);
 	if (!n) return;

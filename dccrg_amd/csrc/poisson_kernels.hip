@@ -57,10 +57,17 @@ __device__ __forceinline__ void block_sum_store(double (&v)[K], double* out) {
 // table (dccrgx_internal.hpp); po_ell / po_fine: the same table with the
 // entries the reference drops (skip neighbors, boundary-boundary pairs) set
 // to -1.
-__global__ void po_cache_kernel(MapCtx m, double l0x, double l0y, double l0z, const uint64_t* __restrict__ slot_ids,
-                                const int32_t* __restrict__ cls, const int32_t* __restrict__ face_ell,
-                                const int32_t* __restrict__ face_fine, size_t n, int32_t* __restrict__ po_ell,
-                                int32_t* __restrict__ po_fine, int32_t* __restrict__ type, PoArrays a) {
+// STRETCHED: the lengths are Stretched_Cartesian_Geometry::get_length's
+// (dccrg_stretched_cartesian_geometry.hpp:317-334; geometry_fill_kernel's
+// expression) from the packed coordinates G, for the cell and for every kept
+// neighbor from its own index along the face's dimension: two cells of one
+// level on either side of a level-0 boundary differ in length.
+template <bool STRETCHED>
+__global__ void po_cache_kernel(MapCtx m, double l0x, double l0y, double l0z, StretchedView G,
+                                const uint64_t* __restrict__ slot_ids, const int32_t* __restrict__ cls,
+                                const int32_t* __restrict__ face_ell, const int32_t* __restrict__ face_fine, size_t n,
+                                int32_t* __restrict__ po_ell, int32_t* __restrict__ po_fine,
+                                int32_t* __restrict__ type, PoArrays a) {
 #pragma clang fp contract(off)
 	const size_t s = size_t(xcd_block()) * BS + threadIdx.x;
 	if (s >= n) return;
@@ -70,10 +77,21 @@ __global__ void po_cache_kernel(MapCtx m, double l0x, double l0y, double l0z, co
 	double f6[6] = {0, 0, 0, 0, 0, 0}, sf = 0;
 	int out_type = t;
 	if (t != PO_SKIP) {
-		const int lvl = map_level(m, slot_ids[s]);
-		const double sc = 1.0 / double(uint64_t(1) << lvl);  // Cartesian get_length (geometry 282-304)
+		// half the length along d of the cell with this id
+		auto stretched_half = [&](uint64_t id, int d) {
+			uint64_t ind[3] = {0, 0, 0};
+			const int l = map_indices(m, id, ind[0], ind[1], ind[2]);
+			const double* c = G.c + G.off[d] + (ind[d] >> m.R);
+			return ((c[1] - c[0]) / double(uint64_t(1) << l)) / 2.0;
+		};
 		double ch[3];
-		for (int d = 0; d < 3; d++) ch[d] = (l0[d] * sc) / 2.0;
+		if constexpr (STRETCHED) {
+			for (int d = 0; d < 3; d++) ch[d] = stretched_half(slot_ids[s], d);
+		} else {
+			const int lvl = map_level(m, slot_ids[s]);
+			const double sc = 1.0 / double(uint64_t(1) << lvl);  // Cartesian get_length (geometry 282-304)
+			for (int d = 0; d < 3; d++) ch[d] = (l0[d] * sc) / 2.0;
+		}
 		// offsets toward the +/- neighbor of each dimension (716-723)
 		double pos[3], neg[3];
 		for (int d = 0; d < 3; d++) {
@@ -85,10 +103,15 @@ __global__ void po_cache_kernel(MapCtx m, double l0x, double l0y, double l0z, co
 			return nt != PO_SKIP && !(t == PO_BOUNDARY && nt == PO_BOUNDARY);  // 922-931
 		};
 		auto note = [&](int dir, int32_t nslot) {  // 725-762
-			const int nl = map_level(m, slot_ids[nslot]);
-			const double nsc = 1.0 / double(uint64_t(1) << nl);
 			const int d = dir >> 1;
-			const double nh = (l0[d] * nsc) / 2.0;
+			double nh;
+			if constexpr (STRETCHED) {
+				nh = stretched_half(slot_ids[nslot], d);
+			} else {
+				const int nl = map_level(m, slot_ids[nslot]);
+				const double nsc = 1.0 / double(uint64_t(1) << nl);
+				nh = (l0[d] * nsc) / 2.0;
+			}
 			if (dir & 1) pos[d] = ch[d] + nh;
 			else neg[d] = -1.0 * (ch[d] + nh);
 		};
@@ -479,12 +502,16 @@ inline unsigned po_blocks(size_t n) {
 
 unsigned k_po_blocks(size_t n) { return po_blocks(n); }
 
-void k_po_cache(const MapCtx& m, const double l0[3], const uint64_t* slot_ids, const int32_t* cls,
-                const int32_t* face_ell, const int32_t* face_fine, size_t n, int32_t* po_ell, int32_t* po_fine,
-                int32_t* type, const PoArrays& a, hipStream_t s) {
+void k_po_cache(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
+                const int32_t* cls, const int32_t* face_ell, const int32_t* face_fine, size_t n, int32_t* po_ell,
+                int32_t* po_fine, int32_t* type, const PoArrays& a, hipStream_t s) {
 	if (!n) return;
-	po_cache_kernel<<<po_blocks(n), BS, 0, s>>>(m, l0[0], l0[1], l0[2], slot_ids, cls, face_ell, face_fine, n, po_ell,
-	                                            po_fine, type, a);
+	if (G.c)
+		po_cache_kernel<true><<<po_blocks(n), BS, 0, s>>>(m, l0[0], l0[1], l0[2], G, slot_ids, cls, face_ell, face_fine,
+		                                                  n, po_ell, po_fine, type, a);
+	else
+		po_cache_kernel<false><<<po_blocks(n), BS, 0, s>>>(m, l0[0], l0[1], l0[2], G, slot_ids, cls, face_ell,
+		                                                   face_fine, n, po_ell, po_fine, type, a);
 	HIP_CHECK(hipGetLastError());
 }
 

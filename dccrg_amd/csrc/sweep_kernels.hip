@@ -2014,11 +2014,15 @@ __global__ void check_rows_kernel(const int32_t* __restrict__ cidx, const int32_
 // (Cartesian_Geometry get_center / get_length, dccrg_cartesian_geometry.hpp:
 // 282-362) of every local cell
 // (+ the block minima of adv_dt_kernel's bound over the values written, when
-// dt_partial is given: the next max_time_step needs no pass of its own)
+// dt_partial is given: the next max_time_step needs no pass of its own).
+// STRETCHED: center and lengths are Stretched_Cartesian_Geometry's
+// (dccrg_stretched_cartesian_geometry.hpp:298-403, geometry_fill_kernel's
+// expressions) from the packed coordinates G.
+template <bool STRETCHED>
 __global__ __launch_bounds__(256) void adv_reset_kernel(MapCtx m, const uint64_t* __restrict__ slot_ids, size_t n,
                                                         double s0, double s1, double l00, double l01, double l02,
-                                                        double* vx, double* vy, double* vz, double* lx, double* ly,
-                                                        double* lz, double* dt_partial) {
+                                                        StretchedView G, double* vx, double* vy, double* vz,
+                                                        double* lx, double* ly, double* lz, double* dt_partial) {
 #pragma clang fp contract(off)
 	__shared__ double red[256];
 	const double st[3] = {s0, s1, 0.0};
@@ -2029,8 +2033,24 @@ __global__ __launch_bounds__(256) void adv_reset_kernel(MapCtx m, const uint64_t
 		const int lvl = map_indices(m, slot_ids[s], ind[0], ind[1], ind[2]);
 		const double sf = 1.0 / double(uint64_t(1) << lvl);
 		double L[3], c[2];
-		for (int d = 0; d < 3; d++) L[d] = l0[d] * sf;
-		for (int d = 0; d < 2; d++) c[d] = st[d] + double(ind[d]) * l0[d] / double(uint64_t(1) << m.R) + L[d] / 2;
+		if constexpr (STRETCHED) {
+			const uint64_t l0i = uint64_t(1) << m.R;
+			for (int d = 0; d < 3; d++) {
+				const uint64_t i0 = ind[d] / l0i;
+				const double c0 = G.c[G.off[d] + i0];
+				const double extent = G.c[G.off[d] + i0 + 1] - c0;
+				L[d] = extent / double(uint64_t(1) << lvl);
+				if (d < 2) {
+					const double length_of_index = extent / double(l0i);
+					const double in_cell = length_of_index * double(ind[d] - i0 * l0i);
+					const double low = c0 + in_cell;
+					c[d] = low + L[d] / 2;
+				}
+			}
+		} else {
+			for (int d = 0; d < 3; d++) L[d] = l0[d] * sf;
+			for (int d = 0; d < 2; d++) c[d] = st[d] + double(ind[d]) * l0[d] / double(uint64_t(1) << m.R) + L[d] / 2;
+		}
 		const double v[3] = {-c[1] + 0.5, +c[0] - 0.5, 0.0};
 		vx[s] = v[0];
 		vy[s] = v[1];
@@ -2517,11 +2537,15 @@ AdvRequests k_adv_requests(const MapCtx& m, const DevMesh& dm, const uint64_t* s
 }
 
 size_t k_adv_reset(const MapCtx& m, const uint64_t* slot_ids, size_t n, const double start[3], const double l0[3],
-                   double* const f[7], hipStream_t s, double* dt_partial) {
+                   const StretchedView& G, double* const f[7], hipStream_t s, double* dt_partial) {
 	if (!n) return 0;
 	const unsigned nb = grid_for(n, 256, kDtPartials);
-	adv_reset_kernel<<<nb, 256, 0, s>>>(m, slot_ids, n, start[0], start[1], l0[0], l0[1], l0[2], f[1], f[2], f[3], f[4],
-	                                    f[5], f[6], dt_partial);
+	if (G.c)
+		adv_reset_kernel<true><<<nb, 256, 0, s>>>(m, slot_ids, n, start[0], start[1], l0[0], l0[1], l0[2], G, f[1], f[2],
+		                                          f[3], f[4], f[5], f[6], dt_partial);
+	else
+		adv_reset_kernel<false><<<nb, 256, 0, s>>>(m, slot_ids, n, start[0], start[1], l0[0], l0[1], l0[2], G, f[1], f[2],
+		                                           f[3], f[4], f[5], f[6], dt_partial);
 	HIP_CHECK(hipGetLastError());
 	return nb;
 }

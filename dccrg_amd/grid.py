@@ -298,8 +298,10 @@ class Dccrg:
         """Stretched_Cartesian_Geometry as the grid's geometry: per dimension
         the length + 1 strictly increasing boundaries of the level-0 cells
         (set_initial_length first).  geometry(), get_existing_cells_at,
-        particles_step and fill_geometry then answer from it; set_geometry
-        returns to Cartesian."""
+        particles_step and fill_geometry then answer from it, and so do the
+        built-in solvers: Poisson_Solve's factors (computed at the next cache
+        pass), advection_initialize and advection_adapt's reset of
+        velocities and lengths.  set_geometry returns to Cartesian."""
         arrs = [np.ascontiguousarray(c, np.float64).ravel() for c in coords]
         if len(arrs) != 3:
             raise ValueError("coordinates of three dimensions are needed")
@@ -955,6 +957,9 @@ class Dccrg:
         check(lib().dccrgx_advection_commit(self.h, density.id))
 
     def advection_initialize(self, fields):
+        """The initial state of tests/advection/initialize.hpp:36-82 from the
+        grid's geometry: Cartesian, or the active stretched geometry's centers
+        and lengths."""
         check(lib().dccrgx_advection_initialize(self.h, self._fids(fields)))
 
     def advection_max_time_step(self, fields):
@@ -1009,7 +1014,9 @@ class Dccrg:
         return tuple(int(x) for x in c)
 
     def advection_adapt(self, fields):
-        """adapt_grid (adapter.hpp:232-309), collective; returns (created, removed)."""
+        """adapt_grid (adapter.hpp:232-309), collective; returns (created, removed).
+        Velocities and lengths are reset from the grid's geometry, Cartesian or
+        the active stretched one."""
         out = np.zeros(2, np.uint64)
         check(lib().dccrgx_advection_adapt(self.h, self._fids(fields), _ptr(out)))
         return int(out[0]), int(out[1])

@@ -51,7 +51,11 @@ class Poisson_Solve:
 
     def cache_system_info(self, cells, grid, cells_to_skip=None, rhs=None, solution=None):
         """827-971: classify (local cells boundary, then skip, then solve) and
-        compute the geometry factors on the device."""
+        compute the geometry factors on the device, from the grid's geometry
+        as it is at this call: Cartesian, or after set_stretched_geometry the
+        get_length of every cell and kept face neighbor.  A geometry set
+        later takes effect at the next cache pass; a solve with
+        cache_is_up_to_date=True keeps these factors."""
         rhs, solution = self._fields(grid, rhs, solution)
         a, pa = _ids(cells)
         b, pb = _ids(cells_to_skip)

@@ -131,9 +131,15 @@ int dccrgx_geometry_batch(dccrgx_grid* g, const uint64_t* ids, size_t n, double*
  * answer with its get_center / get_length (298-403) and get_real_coordinate /
  * get_indices (504-607; a coordinate at a dimension's first boundary belongs
  * to the first cell), the geometry block is the one its write() makes of the
- * coordinates, and the advection sweeps read the length fields.  The Poisson
- * factors, dccrgx_advection_initialize and advection_adapt's reset pass stay
- * Cartesian: they see each dimension's start and first cell length.
+ * coordinates, and the advection sweeps read the length fields.  The built-in
+ * solvers follow it too: dccrgx_poisson_cache computes its factors from the
+ * get_length of every cell and of every kept face neighbor,
+ * dccrgx_advection_initialize takes center and length from it, and
+ * dccrgx_advection_adapt's reset pass writes its velocities, lengths and the
+ * next time step's bound from it (dccrgx_advection_length_source stays 0).
+ * A grid that holds a file block only (dccrgx_set_geometry_block,
+ * load_grid_data) has no coordinates: those three calls then see each
+ * dimension's start and first cell length, as before.
  * dccrgx_set_geometry returns the grid to Cartesian; dccrgx_set_geometry_block
  * and load_grid_data leave a file block only, without coordinates.  The
  * finest cells must be wider than the spacing of doubles at their level-0
@@ -599,7 +605,11 @@ int dccrgx_advection_length_source(dccrgx_grid* g, const int fids[7], int* out);
  * cells default to boundary cells, ids in skip_cells are skipped, ids in
  * solve_cells are solved (non-local ids are ignored, as the reference does);
  * computes the geometry factors (set_scaling_factor 696-819) on the device and
- * halos them.  rhs / solution are fp64 fields.
+ * halos them.  rhs / solution are fp64 fields.  The factors are those of the
+ * geometry at this call, Cartesian or stretched, as in the reference: a later
+ * dccrgx_set_geometry or dccrgx_set_stretched_geometry takes effect at the
+ * next dccrgx_poisson_cache, and a solve without one (cache_is_up_to_date)
+ * keeps the old factors.
  * dccrgx_poisson_solve = Poisson_Solve::solve (251-522, failsafe = 0) or
  * solve_failsafe (531-634, failsafe = 1) with the constructor's parameters
  * (187-201); solution = best solution on return.  *iterations = iterations
