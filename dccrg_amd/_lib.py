@@ -133,6 +133,8 @@ _SIGS = {
     "dccrgx_particles_step": (C.c_int, [vp, C.c_int, C.c_int, P(C.c_double), C.c_double, P(u64)]),
     "dccrgx_particles_follow_mesh": (C.c_int, [vp, C.c_int, C.c_int]),
     "dccrgx_particles_adapt_stats": (C.c_int, [vp, C.c_int, P(u64)]),
+    "dccrgx_particles_deposit": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dccrgx_particles_gather": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, P(C.c_int), C.c_int, C.c_int]),
     "dccrgx_set_send_single_cells": (C.c_int, [vp, C.c_int]),
     "dccrgx_get_send_single_cells": (C.c_int, [vp, P(C.c_int)]),
     "dccrgx_set_field_window": (C.c_int, [vp, C.c_int, sz, sz]),

@@ -2441,6 +2441,25 @@ int dccrgx_particles_adapt_stats(dccrgx_grid* gp, int var_field, uint64_t out[3]
 	});
 }
 
+// particles <-> cell fields: the two halves of the transfer share one weight
+int dccrgx_particles_deposit(dccrgx_grid* gp, int var_field, int record_doubles, int shape, int weight_double,
+                             int out_field, int per_volume) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		particles_deposit(g, var_field, record_doubles, shape, weight_double, out_field, per_volume);
+		return 0;
+	});
+}
+
+int dccrgx_particles_gather(dccrgx_grid* gp, int var_field, int record_doubles, int shape, const int* cell_fields,
+                            int n, int first_double) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		particles_gather(g, var_field, record_doubles, shape, cell_fields, n, first_double);
+		return 0;
+	});
+}
+
 // cells_to_send / cells_to_receive while a balance_load is in progress
 // (initialize_balance_load fills them with the migration lists, 3746-3884)
 int dccrgx_get_migration_cells(dccrgx_grid* gp, int peer, int incoming, uint64_t* ids, size_t cap, size_t* n) {

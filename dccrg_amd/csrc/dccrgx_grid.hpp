@@ -56,6 +56,13 @@ void particles_follow_set(Grid& g, int fid, int K);
 bool particles_follow_check(Grid& g, const Field& f);
 void particles_follow_rebuild(Grid& g, Field& f, const uint64_t* old_ids, size_t n_old_local, const DevMesh& newM,
                               size_t new_n_slots, size_t new_n_local, hipStream_t s);
+// particles <-> cell fields with the weight W(p, c) of dccrgx.h (shape 0 NGP,
+// 1 CIC over leaves): deposit sums q W over the records of a local cell and
+// of the distinct leaves of its neighbors_of into a fixed fp64 field; gather
+// writes sum W F_j[c] of n fixed fp64 fields into doubles first_double .. of
+// every record of a local cell
+void particles_deposit(Grid& g, int fid, int K, int shape, int weight_double, int out_fid, int per_volume);
+void particles_gather(Grid& g, int fid, int K, int shape, const int* cell_fields, int n, int first_double);
 // the active stretched geometry's coordinates on the device (x, then y, then
 // z, packed), uploaded at first use
 const double* stretched_device(Grid& g);

@@ -1154,4 +1154,413 @@ void particles_follow_rebuild(Grid& g, Field& f, const uint64_t* old_ids, size_t
 	for (int k = 0; k < 3; k++) f.adapt_stats[k] = h[k];
 }
 
+// ---------------------------------------------------------------------------
+// Particles <-> cell fields (DESIGN.md "Particles"): a record p held by leaf s
+// gives leaf c the share W(p, c).  Shape 0 (NGP): 1 for c == s.  Shape 1 (CIC
+// over leaves, Cartesian geometry): the cloud is a box the size of s centred
+// on the position clamped into s, W the fraction of its volume inside c (the
+// periodic images of c included), so the receivers are s and the distinct
+// leaves of neighbors_of(s), and every s with W(p, c) > 0 is in
+// neighbors_of(c).  Every product, quotient and sum below is one IEEE
+// operation in the order of dccrgx.h, so a model forms bitwise equal terms;
+// only the order of a sum is the kernel's own.
+//   deposit - a wave per receiving local cell c: its own records 64 at a time,
+//             then the distinct non-empty leaves of its iterator row (sorted by
+//             id: repeats are adjacent) four at a time, 16 lanes each; the
+//             lanes' partial sums meet in a fixed shuffle tree and lane 0
+//             stores.  No atomic decides a sum: two calls give equal bits.
+//   gather  - a thread per record of a local cell (source slot found as in the
+//             locate pass): the sum over s and the distinct leaves of its row,
+//             up to four fields per pass, stored into the record.
+namespace {
+
+struct WGeo {
+	double start[3], l0[3], period[3];  // period: double(length) * l0
+	double inv_fine;                    // 1 / 2^R
+	int per[3];
+	const double* c;  // stretched: the packed coordinates (lengths only), else nullptr
+	uint32_t off[3];
+};
+
+struct CellBox {
+	double lo[3], L[3], hi[3];
+};
+
+// geometry_fill_kernel's low and length of a Cartesian cell.  Its two
+// quotients have powers of two as divisors, 1 / 2^level and along / 2^R: the
+// first is formed from its exponent, the second is the product with 1 / 2^R,
+// both the same bits as the divisions (an fp64 division costs this pass about
+// as much as the rest of a weight's dimension)
+__device__ __forceinline__ void cell_box(const MapCtx& m, const WGeo& G, uint64_t id, CellBox& B) {
+	uint64_t ind[3] = {0, 0, 0};
+	const int lvl = map_indices(m, id, ind[0], ind[1], ind[2]);
+	const double sf = __longlong_as_double((1023ll - (lvl < 0 ? 0 : lvl)) << 52);
+#pragma unroll
+	for (int d = 0; d < 3; d++) {
+		const double along = double(ind[d]) * G.l0[d];
+		const double rel = along * G.inv_fine;
+		B.lo[d] = G.start[d] + rel;
+		B.L[d] = G.l0[d] * sf;
+		B.hi[d] = B.lo[d] + B.L[d];
+	}
+}
+
+// (lx * ly) * lz with geometry_fill_kernel's lengths, Cartesian or stretched
+__device__ __forceinline__ double cell_volume(const MapCtx& m, const WGeo& G, uint64_t id) {
+	uint64_t ind[3] = {0, 0, 0};
+	const int lvl = map_indices(m, id, ind[0], ind[1], ind[2]);
+	const double div = double(uint64_t(1) << (lvl < 0 ? 0 : lvl));
+	double L[3];
+#pragma unroll
+	for (int d = 0; d < 3; d++) {
+		if (G.c) {
+			const uint64_t i0 = ind[d] >> m.R;
+			const double c0 = G.c[G.off[d] + i0];
+			const double extent = G.c[G.off[d] + i0 + 1] - c0;
+			L[d] = extent / div;
+		} else {
+			const double sf = 1.0 / div;
+			L[d] = G.l0[d] * sf;
+		}
+	}
+	const double a = L[0] * L[1];
+	return a * L[2];
+}
+
+__device__ __forceinline__ double overlap_1d(double a, double b, double lo, double hi) {
+	const double top = fmin(b, hi);
+	const double bottom = fmax(a, lo);
+	const double o = top - bottom;
+	return fmax(0.0, o);
+}
+
+// W(p, c) of a record at x held by the cell S, for the receiving cell C
+__device__ __forceinline__ double cic_weight(const WGeo& G, const CellBox& S, const CellBox& C, const double x[3]) {
+	double o[3];
+#pragma unroll
+	for (int d = 0; d < 3; d++) {
+		const double xc = fmin(fmax(x[d], S.lo[d]), S.hi[d]);
+		const double half = S.L[d] / 2;
+		const double a = xc - half;
+		const double b = xc + half;
+		o[d] = overlap_1d(a, b, C.lo[d], C.hi[d]);
+		if (G.per[d]) {
+			const double down = -G.period[d], up = G.period[d];
+			const double om = overlap_1d(a, b, C.lo[d] + down, C.hi[d] + down);
+			const double op = overlap_1d(a, b, C.lo[d] + up, C.hi[d] + up);
+			const double lower = om + o[d];
+			o[d] = lower + op;
+		}
+	}
+	// no overlap in one dimension: the product of the fractions is +0
+	if (o[0] == 0.0 || o[1] == 0.0 || o[2] == 0.0) return 0.0;
+	const double fx = o[0] / S.L[0], fy = o[1] / S.L[1], fz = o[2] / S.L[2];
+	const double fxy = fx * fy;
+	return fxy * fz;
+}
+
+WGeo make_wgeo(Grid& g, bool lengths_only) {
+	WGeo G{};
+	for (int d = 0; d < 3; d++) {
+		G.start[d] = g.start[d];
+		G.l0[d] = g.l0[d];
+		G.period[d] = double(g.len[d]) * g.l0[d];
+		G.per[d] = g.per[d];
+	}
+	G.inv_fine = 1.0 / double(uint64_t(1) << g.R);
+	G.c = nullptr;
+	if (lengths_only && g.str.active) {
+		const StretchedView V = stretched_view(g);
+		G.c = V.c;
+		for (int d = 0; d < 3; d++) G.off[d] = V.off[d];
+	}
+	return G;
+}
+
+constexpr int kDB = 256;    // four waves, one receiving cell each per pass
+constexpr int kDGroup = 16;  // lanes that share one source leaf
+
+struct DArgs {
+	const double* pool;
+	const uint32_t* ofirst;  // n_slots + 1 record offsets
+	const uint64_t* slot_ids;
+	const uint32_t* it_ptr;
+	const int32_t* it_slot;
+	size_t n_local;
+	int K, wd, per_volume;  // wd: the record's double that is q (-1: q = 1)
+	double* out;
+};
+
+// (at least six waves per SIMD: the CIC form fits 80 VGPRs without scratch,
+// and its chains of dependent fp64 operations want the waves: 8.85 -> 7.5 ms
+// on the bench's grid against the four waves of 106 VGPRs)
+template <int SHAPE>
+__global__ __launch_bounds__(kDB) __attribute__((amdgpu_waves_per_eu(6))) void particles_deposit_kernel(const MapCtx m, const WGeo G, const DArgs a) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t grp = lane / kDGroup, gl = lane % kDGroup;
+	const size_t waves = size_t(gridDim.x) * (kDB >> 6);
+	for (size_t c = blockIdx.x * size_t(kDB >> 6) + (threadIdx.x >> 6); c < a.n_local; c += waves) {
+		const uint64_t cid = a.slot_ids[c];
+		CellBox C{};
+		if (SHAPE == 1) cell_box(m, G, cid, C);
+		double sum = 0.0;
+		// the cell's own records
+		for (uint32_t r = a.ofirst[c] + lane, r1 = a.ofirst[c + 1]; r < r1; r += 64) {
+			const double* rec = a.pool + size_t(r) * size_t(a.K);
+			const double q = a.wd < 0 ? 1.0 : rec[a.wd];
+			double w = 1.0;
+			if (SHAPE == 1) {
+				const double x[3] = {rec[0], rec[1], rec[2]};
+				w = cic_weight(G, C, C, x);
+			}
+			const double term = q * w;
+			sum = sum + term;
+		}
+		if (SHAPE == 1) {
+			const uint32_t b = a.it_ptr[c], e = a.it_ptr[c + 1];
+			for (uint32_t j0 = b; j0 < e; j0 += 64) {
+				const uint32_t j = j0 + lane;
+				int32_t s = 0;
+				bool take = false;
+				if (j < e) {
+					s = a.it_slot[j];
+					take = s >= 0 && size_t(s) != c && (j == b || a.it_slot[j - 1] != s) &&
+					       a.ofirst[s + 1] != a.ofirst[s];
+				}
+				// the sources of this part of the row, four at a time: group k
+				// takes the (k + 1)-th lane left in `rem`
+				unsigned long long rem = __ballot(take);
+				while (rem) {
+					unsigned long long mine = rem;
+					for (uint32_t k = 0; k < grp; k++) mine &= mine - 1;
+					const int from = mine ? __ffsll(mine) - 1 : 0;
+					const int32_t sg = __shfl(s, from);
+					if (mine) {
+						CellBox S;
+						cell_box(m, G, a.slot_ids[sg], S);
+						for (uint32_t r = a.ofirst[sg] + gl, r1 = a.ofirst[sg + 1]; r < r1; r += kDGroup) {
+							const double* rec = a.pool + size_t(r) * size_t(a.K);
+							const double q = a.wd < 0 ? 1.0 : rec[a.wd];
+							const double x[3] = {rec[0], rec[1], rec[2]};
+							const double w = cic_weight(G, S, C, x);
+							const double term = q * w;
+							sum = sum + term;
+						}
+					}
+					for (int k = 0; k < 64 / kDGroup; k++) rem &= rem - 1;
+				}
+			}
+		}
+#pragma unroll
+		for (int o = 32; o > 0; o >>= 1) {
+			const double other = __shfl_down(sum, o);
+			sum = sum + other;
+		}
+		if (lane == 0) {
+			if (a.per_volume) sum = sum / cell_volume(m, G, cid);
+			a.out[c] = sum;
+		}
+	}
+}
+
+constexpr int kGF = 4;  // cell fields per gather pass
+
+struct GArgs {
+	double* pool;
+	const uint32_t* ofirst;      // n_local + 1 record offsets
+	const uint32_t* chunk_slot;  // chunks + 1 (chunk_slots_kernel)
+	size_t N;                    // records of the local cells
+	int K, first, nf;            // nf fields into doubles first ..
+	const uint64_t* slot_ids;
+	const uint32_t* it_ptr;
+	const int32_t* it_slot;
+	const double *f0, *f1, *f2, *f3;
+};
+
+template <int SHAPE>
+__global__ __launch_bounds__(kPB) void particles_gather_kernel(const MapCtx m, const WGeo G, const GArgs a) {
+	__shared__ uint32_t s_off[kOffCache];
+	const double* const F[kGF] = {a.f0, a.f1, a.f2, a.f3};
+	const size_t chunks = (a.N + kPB - 1) / kPB;
+	for (size_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
+		const size_t p0 = ch * kPB, p1 = p0 + kPB < a.N ? p0 + kPB : a.N;
+		__syncthreads();
+		const size_t lo = a.chunk_slot[ch], hi = a.chunk_slot[ch + 1];
+		const size_t span = hi - lo + 2;
+		const bool cached = span <= size_t(kOffCache);
+		if (cached)
+			for (size_t i = threadIdx.x; i < span; i += kPB) s_off[i] = a.ofirst[lo + i];
+		__syncthreads();
+		const size_t p = p0 + threadIdx.x;
+		if (p >= p1) continue;
+		const size_t s = cached ? lo + upper_bound_idx<uint32_t>(s_off, 0, span, uint32_t(p)) - 1
+		                        : upper_bound_idx<uint32_t>(a.ofirst, lo, hi + 2, uint32_t(p)) - 1;
+		double* r = a.pool + p * size_t(a.K);
+		double acc[kGF];
+		if (SHAPE == 0) {
+#pragma unroll
+			for (int j = 0; j < kGF; j++) acc[j] = j < a.nf ? F[j][s] : 0.0;
+		} else {
+			const double x[3] = {r[0], r[1], r[2]};
+			CellBox S;
+			cell_box(m, G, a.slot_ids[s], S);
+			const double w0 = cic_weight(G, S, S, x);
+#pragma unroll
+			for (int j = 0; j < kGF; j++) acc[j] = j < a.nf ? w0 * F[j][s] : 0.0;
+			int32_t prev = -1;
+			for (uint32_t e = a.it_ptr[s], e1 = a.it_ptr[s + 1]; e < e1; e++) {
+				const int32_t c = a.it_slot[e];
+				if (c == prev) continue;
+				prev = c;
+				if (c < 0 || size_t(c) == s) continue;
+				CellBox C;
+				cell_box(m, G, a.slot_ids[c], C);
+				const double w = cic_weight(G, S, C, x);
+				if (!(w > 0.0)) continue;
+#pragma unroll
+				for (int j = 0; j < kGF; j++) {
+					if (j < a.nf) {
+						const double term = w * F[j][c];
+						acc[j] = acc[j] + term;
+					}
+				}
+			}
+		}
+#pragma unroll
+		for (int j = 0; j < kGF; j++)
+			if (j < a.nf) r[a.first + j] = acc[j];
+	}
+}
+
+// the checks the two calls share; the record offsets of every slot (empty: no
+// pool).  Returns the number of records in the pool.
+size_t particle_mesh_prepare(Grid& g, Field& f, int K, int shape, bool lengths, DBuf<uint32_t>& ofirst) {
+	DX_REQUIRE(g.initialized, "not initialized");
+	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	DX_REQUIRE(K >= 3, "a particle record has at least 3 doubles (the position)");
+	DX_REQUIRE(shape == 0 || shape == 1, "shape must be 0 (NGP) or 1 (CIC)");
+	if (shape == 1) {
+		DX_REQUIRE(g.hood_len >= 1, "CIC needs a neighborhood length of at least 1");
+		DX_REQUIRE(!g.str.active, "CIC needs a Cartesian geometry (a stretched geometry is set)");
+	}
+	if (shape == 1 || lengths) require_geometry(g);
+	hipStream_t s = g.s_comp;
+	const size_t ns = g.n_slots;
+	if (!ns || !f.voff.p) return 0;
+	const uint64_t rec = uint64_t(K) * sizeof(double);
+	const uint64_t total = var_total(f, ns, s);
+	DX_REQUIRE(total / rec < (uint64_t(1) << 31), "more than 2^31 particles on one process");
+	DBuf<int32_t> flag;
+	ofirst.alloc(ns + 1);
+	flag.alloc(1);
+	HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, s));
+	record_offsets_kernel<<<grid_for(ns + 1, 256), 256, 0, s>>>(f.voff.p, ns + 1, rec, ofirst.p, flag.p);
+	HIP_CHECK(hipGetLastError());
+	int32_t bad = 0;
+	d2h_small(&bad, flag.p, 4, s);
+	DX_REQUIRE(!bad, "a cell's payload is not a multiple of 8 * record_doubles bytes");
+	return size_t(total / rec);
+}
+
+Field& fp64_cell_field(Grid& g, int fid, const char* what) {
+	Field& F = fixed_field(g, fid);
+	DX_REQUIRE(F.elem == 8, std::string(what) + " must be a fixed-size field of 8-byte elements (fp64)");
+	return F;
+}
+
+}  // namespace
+
+void particles_deposit(Grid& g, int fid, int K, int shape, int weight_double, int out_fid, int per_volume) {
+	Field& f = field(g, fid);
+	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	Field& out = fp64_cell_field(g, out_fid, "the deposit's output");
+	DX_REQUIRE(weight_double == -1 || (weight_double >= 3 && weight_double < K) || K < 3,
+	           "weight_double must be -1 (q = 1) or a double of the record past the position (3 <= weight_double < "
+	           "record_doubles)");
+	DBuf<uint32_t> ofirst;
+	const size_t N = particle_mesh_prepare(g, f, K, shape, per_volume != 0, ofirst);
+	const size_t nl = g.n_local;
+	hipStream_t s = g.s_comp;
+	field_written(out);
+	if (!nl) return;
+	double* o = reinterpret_cast<double*>(out.data.p);
+	if (!N) {  // every sum is empty
+		HIP_CHECK(hipMemsetAsync(o, 0, nl * sizeof(double), s));
+		return;
+	}
+	ensure_csr(g);
+	DArgs a{};
+	a.pool = reinterpret_cast<const double*>(f.data.p);
+	a.ofirst = ofirst.p;
+	a.slot_ids = g.slot_ids.p;
+	a.it_ptr = g.it_ptr.p;
+	a.it_slot = g.it_slot.p;
+	a.n_local = nl;
+	a.K = K;
+	a.wd = weight_double;
+	a.per_volume = per_volume ? 1 : 0;
+	a.out = o;
+	const WGeo G = make_wgeo(g, per_volume != 0);
+	const unsigned nb = grid_for(nl, kDB >> 6, 1u << 20);
+	if (shape == 1)
+		particles_deposit_kernel<1><<<nb, kDB, 0, s>>>(g.m, G, a);
+	else
+		particles_deposit_kernel<0><<<nb, kDB, 0, s>>>(g.m, G, a);
+	HIP_CHECK(hipGetLastError());
+	HIP_CHECK(hipStreamSynchronize(s));  // ofirst goes out of scope
+}
+
+void particles_gather(Grid& g, int fid, int K, int shape, const int* cell_fields, int n, int first_double) {
+	Field& f = field(g, fid);
+	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	DX_REQUIRE(n >= 1 && cell_fields, "gather needs at least one cell field");
+	std::vector<const double*> F;
+	for (int j = 0; j < n; j++)
+		F.push_back(reinterpret_cast<const double*>(fp64_cell_field(g, cell_fields[j], "a gathered cell field").data.p));
+	DX_REQUIRE(K < 3 || (first_double >= 3 && first_double + n <= K),
+	           "the gathered doubles must lie in the record past the position (3 <= first_double, first_double + n <= "
+	           "record_doubles)");
+	DBuf<uint32_t> ofirst;
+	const size_t N_all = particle_mesh_prepare(g, f, K, shape, false, ofirst);
+	const size_t nl = g.n_local;
+	hipStream_t s = g.s_comp;
+	if (!N_all || !nl) return;
+	const size_t N = size_t(var_total(f, nl, s) / (uint64_t(K) * sizeof(double)));  // the local cells' records
+	if (!N) return;
+	ensure_csr(g);
+	const size_t chunks = (N + kPB - 1) / kPB;
+	DBuf<uint32_t> chunk_slot;
+	chunk_slot.alloc(chunks + 1);
+	chunk_slots_kernel<<<grid_for(chunks + 1, 256), 256, 0, s>>>(ofirst.p, nl, N, chunks, chunk_slot.p);
+	HIP_CHECK(hipGetLastError());
+	GArgs a{};
+	a.pool = reinterpret_cast<double*>(f.data.p);
+	a.ofirst = ofirst.p;
+	a.chunk_slot = chunk_slot.p;
+	a.N = N;
+	a.K = K;
+	a.slot_ids = g.slot_ids.p;
+	a.it_ptr = g.it_ptr.p;
+	a.it_slot = g.it_slot.p;
+	const WGeo G = make_wgeo(g, false);
+	const unsigned nb = grid_for(N, kPB, 1u << 20);
+	for (int j0 = 0; j0 < n; j0 += kGF) {
+		a.first = first_double + j0;
+		a.nf = n - j0 < kGF ? n - j0 : kGF;
+		const double* p[kGF] = {nullptr, nullptr, nullptr, nullptr};
+		for (int j = 0; j < a.nf; j++) p[j] = F[size_t(j0 + j)];
+		a.f0 = p[0];
+		a.f1 = p[1];
+		a.f2 = p[2];
+		a.f3 = p[3];
+		if (shape == 1)
+			particles_gather_kernel<1><<<nb, kPB, 0, s>>>(g.m, G, a);
+		else
+			particles_gather_kernel<0><<<nb, kPB, 0, s>>>(g.m, G, a);
+		HIP_CHECK(hipGetLastError());
+	}
+	field_written(f);
+	HIP_CHECK(hipStreamSynchronize(s));  // ofirst and chunk_slot go out of scope
+}
+
 }  // namespace dccrgx

@@ -143,6 +143,13 @@ def _split(raw, sizes, dtype):
     return out
 
 
+def _shape(shape):
+    """The particle shape of deposit / gather: "ngp" / "cic", or the C ABI's number."""
+    if isinstance(shape, str):
+        return {"ngp": 0, "cic": 1}[shape.lower()]
+    return int(shape)
+
+
 class TorchExchange:
     """Host transport over torch.distributed point-to-point (gloo): the
     exchange primitive of include/dccrgx.h (dccrgx_exchange_fn)."""
@@ -922,6 +929,33 @@ class Dccrg:
         st = (C.c_uint64 * 3)()
         check(lib().dccrgx_particles_adapt_stats(self.h, field.id, st))
         return dict(zip(("to_children", "to_parents", "lost"), (int(x) for x in st)))
+
+    def particles_deposit(self, field, out, record_doubles=4, weight=3, shape="cic", per_volume=False, halo=False):
+        """out[c] = sum of q W(p, c) over the records of the local cell c and
+        of the distinct leaves of its neighbors_of (copies of remote neighbors
+        included); q = double `weight` of the record (None or -1: 1, a count).
+        shape "ngp" (the record's own cell) or "cic" (a cloud the size of the
+        holding cell, shared by volume; Cartesian geometry).  per_volume
+        divides by the cell's volume.  `out` is a fixed float64 field; its
+        remote copies are not written.  halo=True refreshes the copies of
+        remote neighbors first.  Two calls give bitwise equal fields."""
+        if halo:
+            self.update_copies_of_remote_neighbors()
+        w = -1 if weight is None else int(weight)
+        check(lib().dccrgx_particles_deposit(self.h, field.id, int(record_doubles), _shape(shape), w, out.id,
+                                             int(bool(per_volume))))
+
+    def particles_gather(self, field, cell_fields, first_double, record_doubles, shape="cic", halo=False):
+        """record[first_double + j] = sum of W(p, c) cell_fields[j][c] over the
+        record's cell and the distinct leaves of its neighbors_of, for every
+        record of a local cell; the fixed float64 cell fields' remote copies
+        are read (halo=True refreshes them first).  Nothing else of a record
+        is written.  No renormalisation at an open face."""
+        if halo:
+            self.update_copies_of_remote_neighbors()
+        ids = (C.c_int * len(cell_fields))(*[f.id for f in cell_fields])
+        check(lib().dccrgx_particles_gather(self.h, field.id, int(record_doubles), _shape(shape), ids,
+                                            len(cell_fields), int(first_double)))
 
     # ---- built-in sweeps ------------------------------------------------------------
     def gol_step(self, state: Field, region="all"):

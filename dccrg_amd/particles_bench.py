@@ -14,7 +14,11 @@ records the parent commit's Cartesian lines given with --parent.
 --adapt measures what it costs that the particles follow the mesh
 (Dccrg.particles_follow_mesh): on the same 128^3 base with R = 1 a z-slab of
 one eighth of the cells is refined and merged again, and the two stop_refining
-calls are timed with follow on and off, beside one re-lay of the pool."""
+calls are timed with follow on and off, beside one re-lay of the pool.
+
+--deposit measures the particle <-> mesh transfer on the same grid: CIC and
+NGP Dccrg.particles_deposit (K = 4) and a CIC Dccrg.particles_gather of three
+fields (K = 7), beside the default step and re-lay in the same run."""
 from __future__ import annotations
 
 import argparse
@@ -137,6 +141,10 @@ def main(argv=None):
                    help="particles following the mesh: a z-slab of a base^3, R = 1 grid refined and merged again, "
                         "stop_refining with follow on against follow off (--repeats of each, alternating) and "
                         "against one re-lay of the pool; writes profiles/particles_bench_adapt.json unless --out")
+    p.add_argument("--deposit", action="store_true",
+                   help="charge deposition and field gather: CIC and NGP particles_deposit (K = 4) and a CIC "
+                        "particles_gather of three fields (K = 7) beside the particle step and the re-lay in the "
+                        "same run; writes profiles/particles_bench_deposit.json unless --out")
     p.add_argument("--repeats", type=int, default=3)
     p.add_argument("--parent", default=None,
                    help="with --stretched: files of lines the parent commit's particles_bench printed in the same "
@@ -146,6 +154,8 @@ def main(argv=None):
 
     import torch  # noqa: F401  (one HIP runtime for the process)
 
+    if a.deposit:
+        return main_deposit(a)
     if a.adapt:
         return main_adapt(a)
     if a.stretched:
@@ -313,6 +323,108 @@ def main_adapt(a):
     print(txt, flush=True)
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                 "particles_bench_adapt.json")
+    with open(out, "w") as f:
+        f.write(txt + "\n")
+
+
+def _median_ms(g, call, warmup, steps):
+    """The median of `steps` synchronized calls after `warmup` of them."""
+    for _ in range(warmup):
+        call()
+    g.synchronize()
+    t = []
+    for _ in range(max(steps, 1)):
+        t0 = time.perf_counter()
+        call()
+        g.synchronize()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(t)), t
+
+
+def measure_deposit(a, Kd, what):
+    """Deposit (Kd = 4: position and q) or gather (Kd = 7: position, q and
+    three gathered doubles) on a fresh base^3 periodic grid with ppc records
+    per cell, and one re-lay of that pool."""
+    import dccrg_amd
+    from dccrg_amd._lib import check, lib
+
+    n = a.base
+    g = dccrg_amd.Dccrg(0, 1, 0).set_initial_length((n, n, n)).set_neighborhood_length(1)
+    g.set_maximum_refinement_level(0).set_periodic(True, True, True).initialize()
+    fld = g.add_variable_field("particles", np.float64, True)
+    ids = g.slot_ids()[: g.n_local]
+    nc = ids.size
+    k = (ids - np.uint64(1)).astype(np.int64)
+    ix = np.stack([k % n, (k // n) % n, k // (n * n)], axis=1)
+    rng = np.random.default_rng(1)
+    rec = np.zeros((nc, a.ppc, Kd))
+    rec[:, :, 0:3] = ix.astype(np.float64)[:, None, :] + rng.random((nc, a.ppc, 3))
+    rec[:, :, 3] = rng.random((nc, a.ppc))
+    charge = float(rec[:, :, 3].sum())
+    rec = rec.reshape(-1)
+    fld.resize(np.full(nc, a.ppc * Kd, np.uint64))
+    check(lib().dccrgx_variable_field_upload(g.h, fld.id, 0, nc, rec.ctypes.data_as(C.c_void_p), rec.nbytes))
+    del rec
+    n_particles = nc * a.ppc
+    res = dict(cells=int(nc), particles=int(n_particles), K=Kd)
+    out = g.add_field("rho", np.float64, False)
+    if what == "deposit":
+        for shape in ("cic", "ngp"):
+            ms, runs = _median_ms(g, lambda: g.particles_deposit(fld, out, Kd, 3, shape), a.warmup, a.steps)
+            total = float(out.get(0, nc).sum())
+            assert abs(total - charge) <= 1e-9 * charge, (shape, total, charge)  # a periodic grid keeps every share
+            res[shape] = dict(ms=ms, runs_ms=runs, alg_bytes=n_particles * 8 * Kd + nc * 8)
+    else:
+        fields = [g.add_field(f"F{j}", np.float64, False) for j in range(3)]
+        for j, f in enumerate(fields):
+            f.set(np.full(g.n_slots, 1.0 + j))
+        ms, runs = _median_ms(g, lambda: g.particles_gather(fld, fields, 4, Kd, "cic"), a.warmup, a.steps)
+        got = fld.get(0, 1)[0].reshape(-1, Kd)
+        assert np.allclose(got[:, 4:7], [1.0, 2.0, 3.0], rtol=1e-12), got[:2]  # constant fields come back
+        res["cic"] = dict(ms=ms, runs_ms=runs, fields=3, alg_bytes=n_particles * (8 * Kd + 8 * 3) + nc * 8 * 3)
+    cur = fld.sizes(0, nc) // np.uint64(8)
+    relay, _ = _median_ms(g, lambda: fld.resize(cur), 1, 3)
+    res["relay_ms"] = relay
+    g.close()
+    return res
+
+
+def main_deposit(a):
+    """CIC and NGP deposit (K = 4) and a CIC gather of three fields (K = 7:
+    the three gathered doubles need their place in the record), each the
+    median of the timed calls after the warm-up, beside the particle step and
+    the re-lay of the default bench in the same run."""
+    dep = measure_deposit(a, 4, "deposit")
+    gat = measure_deposit(a, 7, "gather")
+    step = measure(a)
+    n_particles = dep["particles"]
+
+    def row(r, pool):
+        ach = r["alg_bytes"] / (r["ms"] / 1e3) / 1e9
+        return dict(r, particle_updates_per_s=n_particles / (r["ms"] / 1e3), relays=r["ms"] / step["relay_ms"],
+                    relays_of_its_own_pool=r["ms"] / pool["relay_ms"], over_step=r["ms"] / step["ms"],
+                    roofline={"bound": "hbm", "achieved": ach, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                              "frac": ach / PEAK_HBM_GBS})
+
+    line = {"metric": "particles_deposit", "value": n_particles / (dep["cic"]["ms"] / 1e3),
+            "unit": "particle-updates/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_call": dep["cic"]["ms"], "higher_is_better": True, "dtype": "fp64",
+            "config": {"workload": f"particles in cells, {a.base}^3 periodic, R = 0, neighborhood 1, {a.ppc} per cell; "
+                                   "deposit of double 3 with K = 4, gather of three fields into doubles 4..6 with "
+                                   "K = 7; every call synchronized, the median of the timed calls",
+                       "cells": dep["cells"], "particles": n_particles},
+            "deposit_cic": row(dep["cic"], dep), "deposit_ngp": row(dep["ngp"], dep), "gather_cic": row(gat["cic"], gat),
+            "alg_bytes": "deposit: 8 K per record read once + 8 per cell written; gather: 8 K + 8 n per record + "
+                         "8 n per cell",
+            "step": {"what": "particles_step of the default bench (K = 3) in the same run", "ms": step["ms"],
+                     "movers_per_step": step["movers_per_step"]},
+            "relay": {"what": "VariableField.resize, sizes unchanged (copy once): the default bench's K = 3 pool, "
+                              "and the K = 4 and K = 7 pools measured here",
+                      "ms": step["relay_ms"], "ms_K4": dep["relay_ms"], "ms_K7": gat["relay_ms"]}}
+    txt = json.dumps(line)
+    print(txt, flush=True)
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "particles_bench_deposit.json")
     with open(out, "w") as f:
         f.write(txt + "\n")
 

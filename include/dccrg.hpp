@@ -1219,6 +1219,30 @@ public:
 		                                    st.data()));
 		return st;
 	}
+	// particles -> a cell field: out[c] = the sum of q W(p, c) over the records
+	// of the local cell c and of the distinct leaves of its neighbors_of
+	// (copies of remote neighbors included: update them first); q = double
+	// weight_double of a record, -1: q = 1.  shape 0: nearest grid point,
+	// 1: cloud in cell over leaves (Cartesian geometry).  per_volume divides
+	// by the cell's volume.  Two calls give bitwise equal fields.
+	void particles_deposit(const Device_Variable_Field<double>& particles, const Device_Field<double>& out,
+	                       const int record_doubles = 4, const int weight_double = 3, const int shape = 1,
+	                       const bool per_volume = false) {
+		detail::check(dccrgx_particles_deposit(g_, particles.id(), record_doubles, shape, weight_double, out.id(),
+		                                       per_volume ? 1 : 0));
+	}
+	// cell fields -> particles: double first_double + j of every record of a
+	// local cell = the sum of W(p, c) cell_fields[j][c] over the record's cell
+	// and the distinct leaves of its neighbors_of (the fields' remote copies
+	// are read: update them first); nothing else of a record is written
+	void particles_gather(const Device_Variable_Field<double>& particles,
+	                      const std::vector<Device_Field<double>>& cell_fields, const int first_double,
+	                      const int record_doubles, const int shape = 1) {
+		std::vector<int> id;
+		for (const auto& f : cell_fields) id.push_back(f.id());
+		detail::check(dccrgx_particles_gather(g_, particles.id(), record_doubles, shape, id.data(), int(id.size()),
+		                                      first_double));
+	}
 	// the records follow the mesh in every stop_refining: what user code does
 	// from refined_cell_data / unrefined_cell_data, on the device (a refined
 	// parent's records to the child at their position, the removed children's

@@ -470,6 +470,45 @@ int dccrgx_particles_follow_mesh(dccrgx_grid* g, int var_field, int record_doubl
 /* out = {records moved to children, records moved to parents, lost} of this
  * process in the last dccrgx_stop_refining */
 int dccrgx_particles_adapt_stats(dccrgx_grid* g, int var_field, uint64_t out[3]);
+/* Particles <-> cell fields.  A record p held by leaf s gives leaf c the
+ * share W(p, c).  shape 0 (NGP): 1 for c == s, 0 otherwise; the position is
+ * not read.  shape 1 (CIC over leaves, Cartesian geometry): the cloud is a box
+ * the size of s centred on the particle, W the fraction of its volume inside
+ * c; the receivers are s and the distinct leaves of neighbors_of(s).  Every
+ * product, quotient and sum is one IEEE operation, in this order, per
+ * dimension d: a cell of index i (finest units) and level l has
+ * lo = start + (double(i) * l0) / 2^R (dccrgx_geometry_fill's low),
+ * L = l0 * (1 / 2^l), hi = lo + L; xc = min(max(x, lo_s), hi_s) (a record
+ * outside its cell is clamped into it); a = xc - L_s / 2, b = xc + L_s / 2;
+ * o_k = max(0, min(b, hi_c + k P) - max(a, lo_c + k P)) with
+ * P = double(length_d) * l0_d, k = -1, 0, +1 in a periodic dimension and 0
+ * only otherwise, o = (o_-1 + o_0) + o_+1; f_d = o / L_s.  W = (f_x f_y) f_z.
+ * The share of a cloud past a non-periodic face is dropped.
+ *
+ * deposit: for every local cell c, out[c] = the sum of q_p W(p, c) over the
+ * records of c and of the distinct leaves of neighbors_of(c), the copies of
+ * remote neighbors included; q_p = record[weight_double] (3 <= weight_double
+ * < K), or 1 with weight_double == -1.  per_volume != 0 divides the sum by
+ * (lx ly) lz, dccrgx_geometry_fill's lengths, Cartesian or stretched.
+ * out_field is a fixed fp64 field; its remote-copy slots are not written.  No
+ * atomic decides a sum: two calls on one state give bitwise equal fields;
+ * only the order of a sum is unspecified.  DCCRGX_EINVAL: a fixed-size
+ * var_field, an out_field that is no fixed 8-byte field, K < 3, a cell whose
+ * bytes are no multiple of 8 K, weight_double out of range, shape not 0 or 1,
+ * shape 1 with neighborhood length 0 or a stretched geometry (set or a file's
+ * block), per_volume with a stretched block without coordinates. */
+int dccrgx_particles_deposit(dccrgx_grid* g, int var_field, int record_doubles, int shape, int weight_double,
+                             int out_field, int per_volume);
+/* gather: for every record p of a local cell s,
+ * record[first_double + j] = the sum of W(p, c) F_j[c] over s and the
+ * distinct leaves of neighbors_of(s), j < n; F_j = cell_fields[j], fixed fp64
+ * fields whose remote copies are read (update them first).  No
+ * renormalisation at an open face: a field of ones gathers the share of the
+ * cloud inside the grid.  The positions, every other double and the records
+ * of remote copies are not written.  DCCRGX_EINVAL as for deposit, and unless
+ * 3 <= first_double, first_double + n <= K, n >= 1. */
+int dccrgx_particles_gather(dccrgx_grid* g, int var_field, int record_doubles, int shape, const int* cell_fields,
+                            int n, int first_double);
 
 /* set_send_single_cells 6677 / get_send_single_cells 6684: one message per
  * cell (tag = position + 1) instead of one per process.  On, the remote
