@@ -135,6 +135,8 @@ _SIGS = {
     "dccrgx_particles_adapt_stats": (C.c_int, [vp, C.c_int, P(u64)]),
     "dccrgx_particles_deposit": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dccrgx_particles_gather": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, P(C.c_int), C.c_int, C.c_int]),
+    "dccrgx_particles_accelerate": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
+    "dccrgx_gradient": (C.c_int, [vp, C.c_int, P(C.c_int), C.c_double, C.c_int]),
     "dccrgx_set_send_single_cells": (C.c_int, [vp, C.c_int]),
     "dccrgx_get_send_single_cells": (C.c_int, [vp, P(C.c_int)]),
     "dccrgx_set_field_window": (C.c_int, [vp, C.c_int, sz, sz]),

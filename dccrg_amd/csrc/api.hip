@@ -2460,6 +2460,15 @@ int dccrgx_particles_gather(dccrgx_grid* gp, int var_field, int record_doubles, 
 	});
 }
 
+int dccrgx_particles_accelerate(dccrgx_grid* gp, int var_field, int record_doubles, int first_double,
+                                int weight_double, double factor) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		particles_accelerate(g, var_field, record_doubles, first_double, weight_double, factor);
+		return 0;
+	});
+}
+
 // cells_to_send / cells_to_receive while a balance_load is in progress
 // (initialize_balance_load fills them with the migration lists, 3746-3884)
 int dccrgx_get_migration_cells(dccrgx_grid* gp, int peer, int incoming, uint64_t* ids, size_t cap, size_t* n) {
@@ -3389,6 +3398,43 @@ int dccrgx_poisson_field(dccrgx_grid* gp, const char* name, int* fid) {
 				return 0;
 			}
 		throw Error(DCCRGX_ENOTFOUND, "no Poisson field " + std::string(name));
+	});
+}
+
+// the cell-centred gradient of an fp64 cell field over the face table
+// (gradient_kernel, poisson_kernels.hip); every check precedes the first write
+int dccrgx_gradient(dccrgx_grid* gp, int in_field, const int out_fields[3], double scale, int region) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		DX_REQUIRE(g.initialized, "grid not initialized");
+		DX_REQUIRE(out_fields, "null pointer");
+		const char* fp64 = "the gradient's input and outputs must be fixed-size fields of 8-byte elements (fp64)";
+		DX_REQUIRE(fixed_field(g, in_field).elem == 8, fp64);
+		int wanted = 0;
+		for (int d = 0; d < 3; d++) {
+			if (out_fields[d] == -1) continue;
+			DX_REQUIRE(fixed_field(g, out_fields[d]).elem == 8, fp64);
+			DX_REQUIRE(out_fields[d] != in_field, "a gradient output is the input field");
+			for (int e = 0; e < d; e++)
+				DX_REQUIRE(out_fields[e] != out_fields[d], "two gradient outputs are one field");
+			wanted++;
+		}
+		DX_REQUIRE(wanted, "no gradient output wanted (all three are -1)");
+		size_t s0, s1;
+		region_range(g, region, s0, s1);
+		ensure_face(g);
+		double* out[3] = {nullptr, nullptr, nullptr};
+		for (int d = 0; d < 3; d++) {
+			if (out_fields[d] == -1) continue;
+			Field& F = field(g, out_fields[d]);
+			field_written(F);
+			out[d] = reinterpret_cast<double*>(F.data.p);
+		}
+		k_time_begin(g);
+		k_gradient(g.m, g.l0, stretched_view(g), g.slot_ids.p, g.slot_lvl.p, g.face_ell.p, g.face_fine.p,
+		           reinterpret_cast<const double*>(field(g, in_field).data.p), out, scale, s0, s1, g.s_comp);
+		k_time_end(g);
+		return 0;
 	});
 }
 

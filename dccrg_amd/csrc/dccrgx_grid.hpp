@@ -63,6 +63,9 @@ void particles_follow_rebuild(Grid& g, Field& f, const uint64_t* old_ids, size_t
 // every record of a local cell
 void particles_deposit(Grid& g, int fid, int K, int shape, int weight_double, int out_fid, int per_volume);
 void particles_gather(Grid& g, int fid, int K, int shape, const int* cell_fields, int n, int first_double);
+// record[3 + j] += (factor q) record[first_double + j], j < 3, for every
+// record of a local cell (q = record[weight_double], or 1 with -1)
+void particles_accelerate(Grid& g, int fid, int K, int first_double, int weight_double, double factor);
 // the active stretched geometry's coordinates on the device (x, then y, then
 // z, packed), uploaded at first use
 const double* stretched_device(Grid& g);

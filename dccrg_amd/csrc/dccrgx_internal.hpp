@@ -1220,6 +1220,12 @@ void k_po_reduce(int k, const double* part, unsigned nb, double* red, PoScalars*
                  bool scalar, hipStream_t s);
 // all: P x k all-gathered per-rank sums, combined in rank order
 void k_po_scalar(const double* all, int P, int k, PoScalars* st, const PoParams& prm, int stage, hipStream_t s);
+// dccrgx_gradient over the local slots [s0, s1): out[d] (nullptr: not wanted)
+// = scale * the d-component of the gradient of `in` (G.c given: the stretched
+// geometry's lengths); slot_lvl: the level byte of every slot (ensure_face)
+void k_gradient(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
+                const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine, const double* in,
+                double* const out[3], double scale, size_t s0, size_t s1, hipStream_t s);
 
 }  // namespace dccrgx
 

@@ -1462,6 +1462,23 @@ size_t particle_mesh_prepare(Grid& g, Field& f, int K, int shape, bool lengths, 
 	return size_t(total / rec);
 }
 
+// v += (factor q) E for the first N records of the pool (the local cells'):
+// the product rounded, then the sum.  The update does not depend on the
+// holding cell, so no slot is looked up.
+__global__ __launch_bounds__(kPB) void particles_accelerate_kernel(double* __restrict__ pool, size_t N, int K, int first,
+                                                                   int wd, double factor) {
+	for (size_t p = blockIdx.x * size_t(kPB) + threadIdx.x; p < N; p += size_t(gridDim.x) * kPB) {
+		double* r = pool + p * size_t(K);
+		const double k = wd >= 0 ? factor * r[wd] : factor;
+		const double e0 = r[first], e1 = r[first + 1], e2 = r[first + 2];
+		const double v0 = r[3], v1 = r[4], v2 = r[5];
+		const double t0 = k * e0, t1 = k * e1, t2 = k * e2;
+		r[3] = v0 + t0;
+		r[4] = v1 + t1;
+		r[5] = v2 + t2;
+	}
+}
+
 Field& fp64_cell_field(Grid& g, int fid, const char* what) {
 	Field& F = fixed_field(g, fid);
 	DX_REQUIRE(F.elem == 8, std::string(what) + " must be a fixed-size field of 8-byte elements (fp64)");
@@ -1561,6 +1578,31 @@ void particles_gather(Grid& g, int fid, int K, int shape, const int* cell_fields
 	}
 	field_written(f);
 	HIP_CHECK(hipStreamSynchronize(s));  // ofirst and chunk_slot go out of scope
+}
+
+void particles_accelerate(Grid& g, int fid, int K, int first_double, int weight_double, double factor) {
+	Field& f = field(g, fid);
+	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	DX_REQUIRE(K < 3 || (first_double >= 6 && first_double + 3 <= K),
+	           "the field's three doubles must lie in the record past the velocity (6 <= first_double, first_double + 3 "
+	           "<= record_doubles)");
+	DX_REQUIRE(K < 3 || weight_double == -1 ||
+	               (weight_double >= 6 && weight_double < K &&
+	                !(weight_double >= first_double && weight_double < first_double + 3)),
+	           "weight_double must be -1 (q = 1) or a double of the record past the velocity and outside the field's "
+	           "three (6 <= weight_double < record_doubles)");
+	DBuf<uint32_t> ofirst;
+	const size_t N_all = particle_mesh_prepare(g, f, K, 0, false, ofirst);
+	const size_t nl = g.n_local;
+	hipStream_t s = g.s_comp;
+	if (!N_all || !nl) return;
+	const size_t N = size_t(var_total(f, nl, s) / (uint64_t(K) * sizeof(double)));  // the local cells' records
+	if (!N) return;
+	particles_accelerate_kernel<<<grid_for(N, kPB, 1u << 20), kPB, 0, s>>>(reinterpret_cast<double*>(f.data.p), N, K,
+	                                                                       first_double, weight_double, factor);
+	HIP_CHECK(hipGetLastError());
+	field_written(f);
+	HIP_CHECK(hipStreamSynchronize(s));  // ofirst goes out of scope
 }
 
 }  // namespace dccrgx

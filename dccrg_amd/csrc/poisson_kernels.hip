@@ -498,7 +498,122 @@ inline unsigned po_blocks(size_t n) {
 	return unsigned(b ? b : 8);
 }
 
+// dccrgx_gradient (dccrgx.h): the cell-centred gradient of `in` over the
+// unfiltered face table for the local slots [s0, s1), the first-derivative
+// counterpart of set_scaling_factor's second derivative: the same centre
+// distances (own half length + the neighbor's), the same three-point stencil
+// per dimension.  The Poisson classification is not consulted.
+// A neighbor's length along the face's dimension needs its level only
+// (slot_lvl, one byte per slot, made with the face table): neighbors differ by
+// at most one level, the four finer cells of a face are one level up, and
+// under a stretched geometry the neighbor's level-0 cell along d follows from
+// this cell's own indices (the index just past its upper face or just below
+// its lower one, wrapped), so no neighbor id is decoded.
+template <bool STRETCHED>
+__global__ __launch_bounds__(BS) void gradient_kernel(MapCtx m, double l0x, double l0y, double l0z, StretchedView G,
+                                                      const uint64_t* __restrict__ slot_ids,
+                                                      const uint8_t* __restrict__ slot_lvl,
+                                                      const int32_t* __restrict__ face_ell,
+                                                      const int32_t* __restrict__ face_fine,
+                                                      const double* __restrict__ in, double* __restrict__ ox,
+                                                      double* __restrict__ oy, double* __restrict__ oz, double scale,
+                                                      size_t s0, size_t s1) {
+#pragma clang fp contract(off)
+	const size_t s = s0 + size_t(xcd_block()) * BS + threadIdx.x;
+	if (s >= s1) return;
+	// the six face entries of the row (24 bytes, 8-byte aligned) together
+	int32_t ev[6];
+	const int2* row = reinterpret_cast<const int2*>(face_ell + 6 * s);
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		const int2 r = row[k];
+		ev[2 * k] = r.x;
+		ev[2 * k + 1] = r.y;
+	}
+	const int lvl = slot_lvl[s] & 31;
+	const double vc = in[s];
+	// the six neighbor values and levels, gathered before the ordered arithmetic
+	double v[6];
+	int nl[6];
+#pragma unroll
+	for (int dir = 0; dir < 6; dir++) {
+		const int32_t e = ev[dir];
+		v[dir] = 0.0;
+		nl[dir] = lvl;
+		if (e >= 0) {
+			v[dir] = in[e];
+			nl[dir] = slot_lvl[e] & 31;
+		} else if (e < -1) {
+			const int32_t* f = face_fine + 4 * size_t(-2 - e);
+			const double a0 = in[f[0]], a1 = in[f[1]], a2 = in[f[2]], a3 = in[f[3]];
+			v[dir] = ((a0 + a1) + (a2 + a3)) / 4.0;
+			nl[dir] = lvl + 1;
+		}
+	}
+	// lengths along d of the cell and of its two neighbors
+	double lc[3], ln[6];
+	if constexpr (STRETCHED) {
+		uint64_t ind[3] = {0, 0, 0};
+		map_indices(m, slot_ids[s], ind[0], ind[1], ind[2]);
+		const uint64_t size = uint64_t(1) << (m.R - lvl);
+#pragma unroll
+		for (int d = 0; d < 3; d++) {
+			const double* c = G.c + G.off[d];
+			const uint64_t i0 = ind[d] >> m.R;
+			lc[d] = (c[i0 + 1] - c[i0]) / double(uint64_t(1) << lvl);
+			const uint64_t lo = ind[d] == 0 ? m.glen[d] - 1 : ind[d] - 1;
+			const uint64_t hi = ind[d] + size >= m.glen[d] ? 0 : ind[d] + size;
+			const uint64_t in_ = lo >> m.R, ip = hi >> m.R;
+			ln[2 * d] = (c[in_ + 1] - c[in_]) / double(uint64_t(1) << nl[2 * d]);
+			ln[2 * d + 1] = (c[ip + 1] - c[ip]) / double(uint64_t(1) << nl[2 * d + 1]);
+		}
+	} else {
+		const double l0[3] = {l0x, l0y, l0z};
+#pragma unroll
+		for (int d = 0; d < 3; d++) {
+			lc[d] = l0[d] * (1.0 / double(uint64_t(1) << lvl));  // Cartesian get_length
+			ln[2 * d] = l0[d] * (1.0 / double(uint64_t(1) << nl[2 * d]));
+			ln[2 * d + 1] = l0[d] * (1.0 / double(uint64_t(1) << nl[2 * d + 1]));
+		}
+	}
+	double* const out[3] = {ox, oy, oz};
+#pragma unroll
+	for (int d = 0; d < 3; d++) {
+		if (!out[d]) continue;
+		const double hc = lc[d] / 2.0;
+		const bool has_neg = ev[2 * d] != -1, has_pos = ev[2 * d + 1] != -1;
+		const double h_neg = hc + ln[2 * d] / 2.0, h_pos = hc + ln[2 * d + 1] / 2.0;
+		const double dp = v[2 * d + 1] - vc, dn = vc - v[2 * d];
+		double grad = 0.0;
+		if (has_neg && has_pos) {
+			const double tot = h_pos + h_neg;
+			const double a = h_neg / (h_pos * tot);
+			const double b = h_pos / (h_neg * tot);
+			grad = a * dp + b * dn;
+		} else if (has_pos) {
+			grad = dp / h_pos;
+		} else if (has_neg) {
+			grad = dn / h_neg;
+		}
+		out[d][s] = scale * grad;
+	}
+}
+
 }  // namespace
+
+void k_gradient(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
+                const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine, const double* in,
+                double* const out[3], double scale, size_t s0, size_t s1, hipStream_t s) {
+	if (s1 <= s0) return;
+	const unsigned nb = po_blocks(s1 - s0);
+	if (G.c)
+		gradient_kernel<true><<<nb, BS, 0, s>>>(m, l0[0], l0[1], l0[2], G, slot_ids, slot_lvl, face_ell, face_fine, in,
+		                                        out[0], out[1], out[2], scale, s0, s1);
+	else
+		gradient_kernel<false><<<nb, BS, 0, s>>>(m, l0[0], l0[1], l0[2], G, slot_ids, slot_lvl, face_ell, face_fine, in,
+		                                         out[0], out[1], out[2], scale, s0, s1);
+	HIP_CHECK(hipGetLastError());
+}
 
 unsigned k_po_blocks(size_t n) { return po_blocks(n); }
 

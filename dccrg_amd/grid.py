@@ -957,6 +957,29 @@ class Dccrg:
         check(lib().dccrgx_particles_gather(self.h, field.id, int(record_doubles), _shape(shape), ids,
                                             len(cell_fields), int(first_double)))
 
+    def particles_accelerate(self, field, first_double, record_doubles, factor, weight=-1):
+        """record[3 + j] += (factor q) record[first_double + j], j = 0, 1, 2,
+        for every record of a local cell (the product rounded, then the sum);
+        q = double `weight` of the record (None or -1: 1).  The three doubles
+        and the weight lie past the velocity (6 <= first_double, weight)."""
+        w = -1 if weight is None else int(weight)
+        check(lib().dccrgx_particles_accelerate(self.h, field.id, int(record_doubles), int(first_double), w,
+                                                float(factor)))
+
+    def gradient(self, field, out, scale=1.0, region="all", halo=False):
+        """out[d] = scale * the d-component of the cell-centred gradient of the
+        float64 field `field` in every local cell of `region`; `out` is three
+        float64 Fields or Nones (component not wanted).  The remote copies of
+        `field` are read (halo=True refreshes them first), those of the
+        outputs are not written.  include/dccrgx.h states the operator."""
+        if halo:
+            self.update_copies_of_remote_neighbors()
+        out = list(out)
+        if len(out) != 3:
+            raise ValueError("out must hold three Fields or Nones")
+        ids = (C.c_int * 3)(*[-1 if f is None else f.id for f in out])
+        check(lib().dccrgx_gradient(self.h, field.id, ids, float(scale), REGION[region]))
+
     # ---- built-in sweeps ------------------------------------------------------------
     def gol_step(self, state: Field, region="all"):
         check(lib().dccrgx_gol_step(self.h, state.id, REGION[region]))

@@ -18,7 +18,15 @@ calls are timed with follow on and off, beside one re-lay of the pool.
 
 --deposit measures the particle <-> mesh transfer on the same grid: CIC and
 NGP Dccrg.particles_deposit (K = 4) and a CIC Dccrg.particles_gather of three
-fields (K = 7), beside the default step and re-lay in the same run."""
+fields (K = 7), beside the default step and re-lay in the same run.
+
+--pic measures one electrostatic particle-in-cell cycle on the same grid from
+the public calls only (K = 10: position, velocity, q, E): CIC deposit per
+volume, rhs = -(rho - mean rho) with torch on the fields' device arrays, a
+Poisson solve of a fixed iteration count, Dccrg.gradient with scale -1, the
+halo, a CIC gather of E, Dccrg.particles_accelerate and the step with
+per-record velocities, each stage timed on its own, and Dccrg.gradient alone
+on the uniform grid and on --adapt's refined one."""
 from __future__ import annotations
 
 import argparse
@@ -145,6 +153,11 @@ def main(argv=None):
                    help="charge deposition and field gather: CIC and NGP particles_deposit (K = 4) and a CIC "
                         "particles_gather of three fields (K = 7) beside the particle step and the re-lay in the "
                         "same run; writes profiles/particles_bench_deposit.json unless --out")
+    p.add_argument("--pic", action="store_true",
+                   help="the electrostatic particle-in-cell cycle stage by stage (deposit, rhs, solve, halo, gradient, "
+                        "halo, gather, accelerate, step; K = 10) and dccrgx_gradient alone on the uniform and on "
+                        "--adapt's refined grid; writes profiles/particles_bench_pic.json unless --out")
+    p.add_argument("--pic-iterations", type=int, default=10, help="with --pic: BiCG iterations of a solve (min = max)")
     p.add_argument("--repeats", type=int, default=3)
     p.add_argument("--parent", default=None,
                    help="with --stretched: files of lines the parent commit's particles_bench printed in the same "
@@ -154,6 +167,8 @@ def main(argv=None):
 
     import torch  # noqa: F401  (one HIP runtime for the process)
 
+    if a.pic:
+        return main_pic(a)
     if a.deposit:
         return main_deposit(a)
     if a.adapt:
@@ -425,6 +440,177 @@ def main_deposit(a):
     print(txt, flush=True)
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                 "particles_bench_deposit.json")
+    with open(out, "w") as f:
+        f.write(txt + "\n")
+
+
+class _DeviceArray:
+    """A fixed fp64 field's device array as torch sees it (no copy)."""
+
+    def __init__(self, field, n):
+        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "<f8", "data": (int(field.device_ptr()), False),
+                                         "version": 2}
+
+
+def _torch_view(field, n):
+    import torch
+
+    return torch.as_tensor(_DeviceArray(field, n), device="cuda")
+
+
+PIC_K, PIC_Q, PIC_E = 10, 6, 7  # record: position, velocity, q, E
+PIC_STAGES = ("deposit", "rhs", "solve", "halo_phi", "gradient", "halo_E", "gather", "accelerate", "step")
+# gradient_kernel per local cell: phi 8 B + face row 24 B + three outputs 24 B, the minimum; its own level byte and
+# the gathered neighbor values (6 x 8 B) and levels (6 x 1 B) are cache hits on a grid in slot order
+GRADIENT_MIN_BYTES, GRADIENT_GATHER_BYTES = 56, 1 + 6 * 8 + 6
+
+
+def _refine_slab(g, n):
+    """--adapt's mesh: the z-slab of one eighth of a base^3, R = 1 grid refined."""
+    ids = g.slot_ids()[: g.n_local]
+    k = (ids - np.uint64(1)).astype(np.int64)
+    for c in ids[k // (n * n) < max(n // 8, 1)]:
+        g.refine_completely(int(c))
+    g.stop_refining()
+
+
+def measure_gradient(a, refined):
+    """dccrgx_gradient alone on base^3 periodic cells (refined: R = 1 with
+    --adapt's z-slab refined): the median of the synchronized calls."""
+    import dccrg_amd
+
+    n = a.base
+    g = dccrg_amd.Dccrg(0, 1, 0).set_initial_length((n, n, n)).set_neighborhood_length(1)
+    g.set_maximum_refinement_level(1 if refined else 0).set_periodic(True, True, True).initialize()
+    if refined:
+        _refine_slab(g, n)
+    phi = g.add_field("phi", np.float64, False)
+    out = [g.add_field(nm, np.float64, False) for nm in ("Ex", "Ey", "Ez")]
+    phi.set(np.random.default_rng(2).random(g.n_slots))
+    ms, runs = _median_ms(g, lambda: g.gradient(phi, out, -1.0), a.warmup, a.steps)
+    # the same calls between device events (dccrgx_kernel_timing): the kernel without the launch and the
+    # synchronization the host clock includes
+    g.kernel_timing(1)
+    for _ in range(max(a.steps, 1)):
+        g.gradient(phi, out, -1.0)
+    g.synchronize()
+    kms, kn = g.kernel_timing(0)
+    kernel_ms = kms / max(kn, 1)
+    nc = int(g.n_local)
+    g.close()
+
+    def roofline(t):
+        ach = nc * GRADIENT_MIN_BYTES / (t / 1e3) / 1e9
+        return {"bound": "hbm", "achieved": ach, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": ach / PEAK_HBM_GBS}
+
+    return dict(ms=ms, runs_ms=runs, kernel_ms=kernel_ms, kernel_launches=int(kn), cells=nc,
+                min_bytes_per_cell=GRADIENT_MIN_BYTES, gathered_bytes_per_cell=GRADIENT_GATHER_BYTES,
+                roofline=roofline(ms), roofline_kernel=roofline(kernel_ms))
+
+
+def measure_pic(a):
+    """warmup + steps electrostatic cycles on base^3 periodic cells, R = 0, ppc
+    records of K = 10 per cell: every stage synchronized and timed on its own,
+    the medians over the timed cycles."""
+    import torch
+
+    import dccrg_amd
+    from dccrg_amd._lib import check, lib
+
+    n = a.base
+    g = dccrg_amd.Dccrg(0, 1, 0).set_initial_length((n, n, n)).set_neighborhood_length(1)
+    g.set_maximum_refinement_level(0).set_periodic(True, True, True).initialize()
+    fld = g.add_variable_field("particles", np.float64, True)
+    ids = g.slot_ids()[: g.n_local]
+    nc = ids.size
+    k = (ids - np.uint64(1)).astype(np.int64)
+    ix = np.stack([k % n, (k // n) % n, k // (n * n)], axis=1)
+    rng = np.random.default_rng(1)
+    rec = np.zeros((nc, a.ppc, PIC_K))
+    rec[:, :, 0:3] = ix.astype(np.float64)[:, None, :] + rng.random((nc, a.ppc, 3))
+    rec[:, :, 3:6] = 0.2 * (rng.random((nc, a.ppc, 3)) - 0.5)
+    rec[:, :, PIC_Q] = 1 + 0.1 * np.cos(2 * np.pi * rec[:, :, 0] / n)
+    rec = rec.reshape(-1)
+    fld.resize(np.full(nc, a.ppc * PIC_K, np.uint64))
+    check(lib().dccrgx_variable_field_upload(g.h, fld.id, 0, nc, rec.ctypes.data_as(C.c_void_p), rec.nbytes))
+    del rec
+    n_particles = nc * a.ppc
+    rho = g.add_field("rho", np.float64, False)
+    rhs = g.add_field("rhs", np.float64, False)
+    phi = g.add_field("solution", np.float64, True)
+    E = [g.add_field(nm, np.float64, True) for nm in ("Ex", "Ey", "Ez")]
+    solver = dccrg_amd.Poisson_Solve(max_iterations=a.pic_iterations, min_iterations=a.pic_iterations)
+    solver.cache_system_info(ids, g, rhs=rhs, solution=phi)
+    t_rho, t_rhs = _torch_view(rho, nc), _torch_view(rhs, nc)
+    factor = [0.0]
+
+    def make_rhs():
+        torch.sub(t_rho.mean(), t_rho, out=t_rhs)  # -(rho - mean rho)
+        torch.cuda.synchronize()
+
+    stages = {
+        "deposit": lambda: g.particles_deposit(fld, rho, PIC_K, PIC_Q, "cic", per_volume=True),
+        "rhs": make_rhs,
+        "solve": lambda: solver.solve(ids, g, cache_is_up_to_date=True, rhs=rhs, solution=phi),
+        "halo_phi": g.update_copies_of_remote_neighbors,
+        "gradient": lambda: g.gradient(phi, E, -1.0),
+        "halo_E": g.update_copies_of_remote_neighbors,
+        "gather": lambda: g.particles_gather(fld, E, PIC_E, PIC_K, "cic"),
+        "accelerate": lambda: g.particles_accelerate(fld, PIC_E, PIC_K, factor[0], PIC_Q),
+        "step": lambda: g.particles_step(fld, PIC_K, None, 1.0),
+    }
+    times = {s: [] for s in PIC_STAGES}
+    cycles = a.warmup + max(a.steps, 1)
+    st = None
+    for cycle in range(cycles):
+        for s in PIC_STAGES:
+            g.synchronize()
+            t0 = time.perf_counter()
+            r = stages[s]()
+            g.synchronize()
+            if cycle >= a.warmup:
+                times[s].append((time.perf_counter() - t0) * 1e3)
+            if s == "gradient" and cycle == 0:
+                # the kick of all cycles together stays below 0.01 cell lengths a step
+                emax = max(float(_torch_view(f, nc).abs().max()) for f in E)
+                factor[0] = 0.01 / (1.1 * max(emax, 1e-300) * cycles)
+            if s == "step":
+                st = r
+    assert st["lost"] == 0 and st["stayed"] + st["moved"] == n_particles, st
+    left = int(fld.sizes(0, nc).sum()) // (8 * PIC_K)
+    assert left == n_particles, left
+    g.close()
+    med = {s: float(np.median(times[s])) for s in PIC_STAGES}
+    return dict(cells=int(nc), particles=int(n_particles), K=PIC_K, solve_iterations=a.pic_iterations,
+                ms=med, sum_ms=float(sum(med.values())), runs_ms=times, accelerate_factor=factor[0])
+
+
+def main_pic(a):
+    """The electrostatic cycle stage by stage, and dccrgx_gradient alone on
+    the uniform grid and on --adapt's refined one."""
+    pic = measure_pic(a)
+    grad = measure_gradient(a, False)
+    grad_refined = measure_gradient(a, True)
+    new = pic["ms"]["gradient"] + pic["ms"]["accelerate"]
+    line = {"metric": "pic_cycle", "value": pic["particles"] / (pic["sum_ms"] / 1e3), "unit": "particle-updates/s",
+            "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_cycle": pic["sum_ms"], "higher_is_better": True,
+            "dtype": "fp64",
+            "config": {"workload": f"electrostatic particle-in-cell cycle, {a.base}^3 periodic, R = 0, neighborhood 1, "
+                                   f"{a.ppc} records of K = {PIC_K} per cell: CIC deposit per volume, rhs = -(rho - mean) "
+                                   f"with torch on the fields' device arrays, {a.pic_iterations} BiCG iterations "
+                                   "(min = max), gradient with scale -1, CIC gather of three fields, accelerate, step "
+                                   "with per-record velocities; every stage synchronized, medians over the timed cycles",
+                       "cells": pic["cells"], "particles": pic["particles"]},
+            "stages_ms": pic["ms"], "sum_ms": pic["sum_ms"],
+            "gradient_plus_accelerate": {"ms": new, "share_of_cycle": new / pic["sum_ms"]},
+            "accelerate_factor": pic["accelerate_factor"], "runs_ms": pic["runs_ms"],
+            "gradient": grad, "gradient_refined": grad_refined,
+            "gradient_bytes": "minimum per cell: phi 8 + face row 24 + three outputs 24 = 56; gathered through the "
+                              "caches: the cell's level byte, six neighbor values (48) and six level bytes"}
+    txt = json.dumps(line)
+    print(txt, flush=True)
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "particles_bench_pic.json")
     with open(out, "w") as f:
         f.write(txt + "\n")
 

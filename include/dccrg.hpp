@@ -1243,6 +1243,23 @@ public:
 		detail::check(dccrgx_particles_gather(g_, particles.id(), record_doubles, shape, id.data(), int(id.size()),
 		                                      first_double));
 	}
+	// v += (factor q) E: doubles 3..5 of every record of a local cell take
+	// factor * q times doubles first_double .. first_double + 2 (q = double
+	// weight_double, -1: q = 1); nothing else of a record is written
+	void particles_accelerate(const Device_Variable_Field<double>& particles, const int first_double,
+	                          const int record_doubles, const double factor, const int weight_double = -1) {
+		detail::check(dccrgx_particles_accelerate(g_, particles.id(), record_doubles, first_double, weight_double,
+		                                          factor));
+	}
+	// out[d] = scale * the d-component of the cell-centred gradient of `in`
+	// over the leaves (dccrgx.h states the operator; nullptr: component not
+	// wanted); in's remote copies are read: update them first
+	void gradient(const Device_Field<double>& in, const std::array<const Device_Field<double>*, 3>& out,
+	              const double scale = 1.0, const int region = DCCRGX_REGION_ALL) {
+		int id[3];
+		for (int d = 0; d < 3; d++) id[d] = out[size_t(d)] ? out[size_t(d)]->id() : -1;
+		detail::check(dccrgx_gradient(g_, in.id(), id, scale, region));
+	}
 	// the records follow the mesh in every stop_refining: what user code does
 	// from refined_cell_data / unrefined_cell_data, on the device (a refined
 	// parent's records to the child at their position, the removed children's

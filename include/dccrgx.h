@@ -509,6 +509,43 @@ int dccrgx_particles_deposit(dccrgx_grid* g, int var_field, int record_doubles, 
  * 3 <= first_double, first_double + n <= K, n >= 1. */
 int dccrgx_particles_gather(dccrgx_grid* g, int var_field, int record_doubles, int shape, const int* cell_fields,
                             int n, int first_double);
+/* accelerate: for every record of a local cell, k = factor * q with
+ * q = record[weight_double], or q = 1 with weight_double == -1 (then
+ * k = factor), and record[3 + j] = record[3 + j] + k * record[first_double + j]
+ * for j = 0, 1, 2, the product rounded first and then the sum.  Nothing else of
+ * a record and no record of a remote copy is written.  DCCRGX_EINVAL as for
+ * gather (no shape is taken), and unless 6 <= first_double,
+ * first_double + 3 <= K, and weight_double is -1 or in [6, K) outside
+ * [first_double, first_double + 3). */
+int dccrgx_particles_accelerate(dccrgx_grid* g, int var_field, int record_doubles, int first_double,
+                                int weight_double, double factor);
+/* The cell-centred gradient of the fixed fp64 field in_field over the leaves:
+ * out_fields[d] (fixed fp64 fields, -1: component not wanted) of every local
+ * cell of `region` (DCCRGX_REGION_*; inner then outer writes the bits of all)
+ * = scale * grad_d.  The remote copies of in_field are read (update them
+ * first); remote-copy slots of the outputs are never written.  The operator is
+ * the first-derivative counterpart of dccrgx_poisson_cache's factors
+ * (set_scaling_factor 696-819): the same centre distances and three-point
+ * stencil per dimension, so that on a periodic uniform grid the sum over cells
+ * of (A phi)(grad_d phi) is zero.  Every product, quotient, sum and difference
+ * is one IEEE operation in this order.  For a local leaf c and dimension d:
+ * hc = L_c,d / 2 with L the length dccrgx_poisson_cache uses (Cartesian
+ * l0_d * (1 / 2^level); stretched (c[i + 1] - c[i]) / 2^level from the cell's
+ * own level-0 index i along d; a grid that holds only a stretched file block
+ * without coordinates sees each dimension's start and first cell length).  A
+ * side has a neighbor unless the cell has no face neighbor there (a grid edge
+ * of a non-periodic dimension); then h = hc + L_n,d / 2 with the neighbor's
+ * own length and v = in[n], or for four finer neighbors their sum (in an
+ * unspecified order) divided by 4.0.  Both sides: tot = h_pos + h_neg,
+ * a = h_neg / (h_pos * tot), b = h_pos / (h_neg * tot),
+ * grad = a * (v_pos - v_c) + b * (v_c - v_neg).  Only the + side:
+ * grad = (v_pos - v_c) / h_pos; only the - side: (v_c - v_neg) / h_neg;
+ * neither: 0.  A cell that is its own periodic neighbor gets 0 from the same
+ * formula.  The Poisson solver's skip / boundary classification is not
+ * consulted: every leaf takes part.  DCCRGX_EINVAL: a variable-size field or
+ * one that is not 8 bytes wide, an output equal to the input or to another
+ * output, all three outputs -1, a bad region. */
+int dccrgx_gradient(dccrgx_grid* g, int in_field, const int out_fields[3], double scale, int region);
 
 /* set_send_single_cells 6677 / get_send_single_cells 6684: one message per
  * cell (tag = position + 1) instead of one per process.  On, the remote
