@@ -136,6 +136,9 @@ _SIGS = {
     "dccrgx_particles_deposit": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dccrgx_particles_gather": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, P(C.c_int), C.c_int, C.c_int]),
     "dccrgx_particles_accelerate": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
+    "dccrgx_particles_deposit_moments": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_int),
+                                                   C.c_int, C.c_int]),
+    "dccrgx_particles_boris": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
     "dccrgx_gradient": (C.c_int, [vp, C.c_int, P(C.c_int), C.c_double, C.c_int]),
     "dccrgx_set_send_single_cells": (C.c_int, [vp, C.c_int]),
     "dccrgx_get_send_single_cells": (C.c_int, [vp, P(C.c_int)]),

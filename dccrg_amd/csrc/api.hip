@@ -2469,6 +2469,25 @@ int dccrgx_particles_accelerate(dccrgx_grid* gp, int var_field, int record_doubl
 	});
 }
 
+int dccrgx_particles_deposit_moments(dccrgx_grid* gp, int var_field, int record_doubles, int shape, int weight_double,
+                                     const int* factors, const int* out_fields, int n, int per_volume) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		particles_deposit_moments(g, var_field, record_doubles, shape, weight_double, factors, out_fields, n,
+		                          per_volume);
+		return 0;
+	});
+}
+
+int dccrgx_particles_boris(dccrgx_grid* gp, int var_field, int record_doubles, int e_first, int b_first,
+                           int weight_double, double factor) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		particles_boris(g, var_field, record_doubles, e_first, b_first, weight_double, factor);
+		return 0;
+	});
+}
+
 // cells_to_send / cells_to_receive while a balance_load is in progress
 // (initialize_balance_load fills them with the migration lists, 3746-3884)
 int dccrgx_get_migration_cells(dccrgx_grid* gp, int peer, int incoming, uint64_t* ids, size_t cap, size_t* n) {

@@ -66,6 +66,14 @@ void particles_gather(Grid& g, int fid, int K, int shape, const int* cell_fields
 // record[3 + j] += (factor q) record[first_double + j], j < 3, for every
 // record of a local cell (q = record[weight_double], or 1 with -1)
 void particles_accelerate(Grid& g, int fid, int K, int first_double, int weight_double, double factor);
+// n moments (q * record[factors[2 j]]) * record[factors[2 j + 1]] (-1: 1.0) of
+// the records in the deposit's walk, W formed once per (record, receiver);
+// factors (-1, -1) give the deposit's bits
+void particles_deposit_moments(Grid& g, int fid, int K, int shape, int weight_double, const int* factors,
+                               const int* out_fids, int n, int per_volume);
+// the Boris kick of dccrgx.h with E at e_first .., B at b_first ..,
+// h = factor q, for every record of a local cell
+void particles_boris(Grid& g, int fid, int K, int e_first, int b_first, int weight_double, double factor);
 // the active stretched geometry's coordinates on the device (x, then y, then
 // z, packed), uploaded at first use
 const double* stretched_device(Grid& g);

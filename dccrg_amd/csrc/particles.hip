@@ -1363,6 +1363,119 @@ __global__ __launch_bounds__(kDB) __attribute__((amdgpu_waves_per_eu(6))) void p
 	}
 }
 
+// Several moments of the records in one walk (dccrgx_particles_deposit_moments):
+// the deposit's walk, lane for lane and shuffle for shuffle, with W(p, c)
+// formed once per (record, receiver) and fed to M accumulators.  A call with
+// more moments than kMW runs several passes, full ones first.  (DESIGN.md
+// "Moments in one deposit pass" has the resource report and the measurements
+// the width was chosen from.)
+#ifndef DCCRGX_MOMENTS_WIDTH
+#define DCCRGX_MOMENTS_WIDTH 5
+#endif
+constexpr int kMW = DCCRGX_MOMENTS_WIDTH;  // moments per pass (the define is for A/B builds of a narrower width)
+static_assert(kMW >= 1 && kMW <= 5, "six accumulators and more spill to scratch even at four waves per SIMD");
+// waves per SIMD asked of the compiler: up to three accumulators fit the
+// deposit's 80 VGPRs, four need 96 (five waves), five 123 (four waves: ten
+// moments in two passes measured 25.2 ms against 29.6 ms in passes of 4, 4
+// and 2); none uses scratch
+constexpr int moments_waves(int M) { return M <= 3 ? 6 : M == 4 ? 5 : 4; }
+
+// (a kernel parameter of its own, read with unrolled constant indices only:
+// the factor indices and the outputs stay in SGPRs, see PArgs)
+struct MArgs {
+	int fu[kMW], fv[kMW];  // m_j = (q * record[fu[j]]) * record[fv[j]]; -1: 1.0
+	double* out[kMW];
+};
+
+template <int M>
+__device__ __forceinline__ void moments_add(const double* rec, double q, double w, const MArgs& f, double (&sum)[M]) {
+#pragma unroll
+	for (int j = 0; j < M; j++) {
+		// (a factor of -1 costs no load, and the product with 1.0 is kept:
+		// loading double 0 instead and dropping it, or branching round the
+		// product, both measured slower)
+		const double u = f.fu[j] < 0 ? 1.0 : rec[f.fu[j]];
+		const double v = f.fv[j] < 0 ? 1.0 : rec[f.fv[j]];
+		const double qu = q * u;
+		const double mj = qu * v;
+		const double term = mj * w;
+		sum[j] = sum[j] + term;
+	}
+}
+
+template <int SHAPE, int M>
+__global__ __launch_bounds__(kDB) __attribute__((amdgpu_waves_per_eu(moments_waves(M)))) void particles_moments_kernel(
+    const MapCtx m, const WGeo G, const DArgs a, const MArgs f) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t grp = lane / kDGroup, gl = lane % kDGroup;
+	const size_t waves = size_t(gridDim.x) * (kDB >> 6);
+	for (size_t c = blockIdx.x * size_t(kDB >> 6) + (threadIdx.x >> 6); c < a.n_local; c += waves) {
+		const uint64_t cid = a.slot_ids[c];
+		CellBox C{};
+		if (SHAPE == 1) cell_box(m, G, cid, C);
+		double sum[M];
+#pragma unroll
+		for (int j = 0; j < M; j++) sum[j] = 0.0;
+		// the cell's own records
+		for (uint32_t r = a.ofirst[c] + lane, r1 = a.ofirst[c + 1]; r < r1; r += 64) {
+			const double* rec = a.pool + size_t(r) * size_t(a.K);
+			const double q = a.wd < 0 ? 1.0 : rec[a.wd];
+			double w = 1.0;
+			if (SHAPE == 1) {
+				const double x[3] = {rec[0], rec[1], rec[2]};
+				w = cic_weight(G, C, C, x);
+			}
+			moments_add<M>(rec, q, w, f, sum);
+		}
+		if (SHAPE == 1) {
+			const uint32_t b = a.it_ptr[c], e = a.it_ptr[c + 1];
+			for (uint32_t j0 = b; j0 < e; j0 += 64) {
+				const uint32_t j = j0 + lane;
+				int32_t s = 0;
+				bool take = false;
+				if (j < e) {
+					s = a.it_slot[j];
+					take = s >= 0 && size_t(s) != c && (j == b || a.it_slot[j - 1] != s) &&
+					       a.ofirst[s + 1] != a.ofirst[s];
+				}
+				// the sources of this part of the row, four at a time, as the deposit
+				unsigned long long rem = __ballot(take);
+				while (rem) {
+					unsigned long long mine = rem;
+					for (uint32_t k = 0; k < grp; k++) mine &= mine - 1;
+					const int from = mine ? __ffsll(mine) - 1 : 0;
+					const int32_t sg = __shfl(s, from);
+					if (mine) {
+						CellBox S;
+						cell_box(m, G, a.slot_ids[sg], S);
+						for (uint32_t r = a.ofirst[sg] + gl, r1 = a.ofirst[sg + 1]; r < r1; r += kDGroup) {
+							const double* rec = a.pool + size_t(r) * size_t(a.K);
+							const double q = a.wd < 0 ? 1.0 : rec[a.wd];
+							const double x[3] = {rec[0], rec[1], rec[2]};
+							const double w = cic_weight(G, S, C, x);
+							moments_add<M>(rec, q, w, f, sum);
+						}
+					}
+					for (int k = 0; k < 64 / kDGroup; k++) rem &= rem - 1;
+				}
+			}
+		}
+#pragma unroll
+		for (int j = 0; j < M; j++) {
+#pragma unroll
+			for (int o = 32; o > 0; o >>= 1) {
+				const double other = __shfl_down(sum[j], o);
+				sum[j] = sum[j] + other;
+			}
+		}
+		if (lane == 0) {
+			const double V = a.per_volume ? cell_volume(m, G, cid) : 1.0;
+#pragma unroll
+			for (int j = 0; j < M; j++) f.out[j][c] = a.per_volume ? sum[j] / V : sum[j];
+		}
+	}
+}
+
 constexpr int kGF = 4;  // cell fields per gather pass
 
 struct GArgs {
@@ -1479,6 +1592,44 @@ __global__ __launch_bounds__(kPB) void particles_accelerate_kernel(double* __res
 	}
 }
 
+// the Boris kick of dccrgx.h for the first N records of the pool: half the
+// electric kick, the rotation about B, the other half; every operation
+// rounded on its own (fp contract is off in this file)
+__global__ __launch_bounds__(kPB) void particles_boris_kernel(double* __restrict__ pool, size_t N, int K, int ef, int bf,
+                                                              int wd, double factor) {
+	for (size_t p = blockIdx.x * size_t(kPB) + threadIdx.x; p < N; p += size_t(gridDim.x) * kPB) {
+		double* r = pool + p * size_t(K);
+		const double h = wd >= 0 ? factor * r[wd] : factor;
+		const double e0 = r[ef], e1 = r[ef + 1], e2 = r[ef + 2];
+		const double b0 = r[bf], b1 = r[bf + 1], b2 = r[bf + 2];
+		const double v0 = r[3], v1 = r[4], v2 = r[5];
+		const double he0 = h * e0, he1 = h * e1, he2 = h * e2;
+		const double m0 = v0 + he0, m1 = v1 + he1, m2 = v2 + he2;
+		const double t0 = h * b0, t1 = h * b1, t2 = h * b2;
+		const double t00 = t0 * t0, t11 = t1 * t1, t22 = t2 * t2;
+		const double t01 = t00 + t11;
+		const double tt = t01 + t22;
+		const double den = 1.0 + tt;
+		const double d0 = 2.0 * t0, d1 = 2.0 * t1, d2 = 2.0 * t2;
+		const double s0 = d0 / den, s1 = d1 / den, s2 = d2 / den;
+		// c = vm x t
+		const double c0a = m1 * t2, c0b = m2 * t1;
+		const double c1a = m2 * t0, c1b = m0 * t2;
+		const double c2a = m0 * t1, c2b = m1 * t0;
+		const double c0 = c0a - c0b, c1 = c1a - c1b, c2 = c2a - c2b;
+		const double p0 = m0 + c0, p1 = m1 + c1, p2 = m2 + c2;
+		// d = vp x s
+		const double g0a = p1 * s2, g0b = p2 * s1;
+		const double g1a = p2 * s0, g1b = p0 * s2;
+		const double g2a = p0 * s1, g2b = p1 * s0;
+		const double g0 = g0a - g0b, g1 = g1a - g1b, g2 = g2a - g2b;
+		const double q0 = m0 + g0, q1 = m1 + g1, q2 = m2 + g2;
+		r[3] = q0 + he0;
+		r[4] = q1 + he1;
+		r[5] = q2 + he2;
+	}
+}
+
 Field& fp64_cell_field(Grid& g, int fid, const char* what) {
 	Field& F = fixed_field(g, fid);
 	DX_REQUIRE(F.elem == 8, std::string(what) + " must be a fixed-size field of 8-byte elements (fp64)");
@@ -1524,6 +1675,86 @@ void particles_deposit(Grid& g, int fid, int K, int shape, int weight_double, in
 	else
 		particles_deposit_kernel<0><<<nb, kDB, 0, s>>>(g.m, G, a);
 	HIP_CHECK(hipGetLastError());
+	HIP_CHECK(hipStreamSynchronize(s));  // ofirst goes out of scope
+}
+
+namespace {
+
+// one pass of exactly `width` moments (1 .. kMW): a missing instantiation is an error
+template <int M>
+void moments_launch(int width, int shape, unsigned nb, hipStream_t s, const MapCtx& m, const WGeo& G, const DArgs& a,
+                    const MArgs& f) {
+	if (width == M) {
+		if (shape == 1)
+			particles_moments_kernel<1, M><<<nb, kDB, 0, s>>>(m, G, a, f);
+		else
+			particles_moments_kernel<0, M><<<nb, kDB, 0, s>>>(m, G, a, f);
+		return;
+	}
+	if constexpr (M > 1)
+		moments_launch<M - 1>(width, shape, nb, s, m, G, a, f);
+	else
+		DX_REQUIRE(false, "no moments kernel of this width");
+}
+
+}  // namespace
+
+void particles_deposit_moments(Grid& g, int fid, int K, int shape, int weight_double, const int* factors,
+                               const int* out_fids, int n, int per_volume) {
+	Field& f = field(g, fid);
+	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	DX_REQUIRE(n >= 1 && n <= 16, "the number of moments must be 1 .. 16");
+	DX_REQUIRE(factors && out_fids, "null pointer");
+	std::vector<double*> outs;
+	for (int j = 0; j < n; j++) {
+		Field& o = fp64_cell_field(g, out_fids[j], "a moment's output");
+		for (int i = 0; i < j; i++)
+			DX_REQUIRE(out_fids[i] != out_fids[j], "two moments share an output field");
+		outs.push_back(reinterpret_cast<double*>(o.data.p));
+	}
+	DX_REQUIRE(weight_double == -1 || (weight_double >= 3 && weight_double < K) || K < 3,
+	           "weight_double must be -1 (q = 1) or a double of the record past the position (3 <= weight_double < "
+	           "record_doubles)");
+	for (int j = 0; j < 2 * n; j++)
+		DX_REQUIRE(factors[j] == -1 || (factors[j] >= 3 && factors[j] < K) || K < 3,
+		           "a moment factor must be -1 (1.0) or a double of the record past the position (3 <= factor < "
+		           "record_doubles)");
+	DBuf<uint32_t> ofirst;
+	const size_t N = particle_mesh_prepare(g, f, K, shape, per_volume != 0, ofirst);
+	const size_t nl = g.n_local;
+	hipStream_t s = g.s_comp;
+	for (int j = 0; j < n; j++) field_written(fixed_field(g, out_fids[j]));
+	if (!nl) return;
+	if (!N) {  // every sum is empty
+		for (int j = 0; j < n; j++) HIP_CHECK(hipMemsetAsync(outs[size_t(j)], 0, nl * sizeof(double), s));
+		return;
+	}
+	ensure_csr(g);
+	DArgs a{};
+	a.pool = reinterpret_cast<const double*>(f.data.p);
+	a.ofirst = ofirst.p;
+	a.slot_ids = g.slot_ids.p;
+	a.it_ptr = g.it_ptr.p;
+	a.it_slot = g.it_slot.p;
+	a.n_local = nl;
+	a.K = K;
+	a.wd = weight_double;
+	a.per_volume = per_volume ? 1 : 0;
+	a.out = nullptr;
+	const WGeo G = make_wgeo(g, per_volume != 0);
+	const unsigned nb = grid_for(nl, kDB >> 6, 1u << 20);
+	for (int j0 = 0; j0 < n; j0 += kMW) {
+		const int width = n - j0 < kMW ? n - j0 : kMW;
+		MArgs ma{};
+		for (int j = 0; j < kMW; j++) {
+			const bool on = j < width;
+			ma.fu[j] = on ? factors[2 * (j0 + j)] : -1;
+			ma.fv[j] = on ? factors[2 * (j0 + j) + 1] : -1;
+			ma.out[j] = on ? outs[size_t(j0 + j)] : nullptr;
+		}
+		moments_launch<kMW>(width, shape, nb, s, g.m, G, a, ma);
+		HIP_CHECK(hipGetLastError());
+	}
 	HIP_CHECK(hipStreamSynchronize(s));  // ofirst goes out of scope
 }
 
@@ -1600,6 +1831,37 @@ void particles_accelerate(Grid& g, int fid, int K, int first_double, int weight_
 	if (!N) return;
 	particles_accelerate_kernel<<<grid_for(N, kPB, 1u << 20), kPB, 0, s>>>(reinterpret_cast<double*>(f.data.p), N, K,
 	                                                                       first_double, weight_double, factor);
+	HIP_CHECK(hipGetLastError());
+	field_written(f);
+	HIP_CHECK(hipStreamSynchronize(s));  // ofirst goes out of scope
+}
+
+void particles_boris(Grid& g, int fid, int K, int e_first, int b_first, int weight_double, double factor) {
+	Field& f = field(g, fid);
+	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	DX_REQUIRE(K < 3 || (e_first >= 6 && e_first + 3 <= K),
+	           "E's three doubles must lie in the record past the velocity (6 <= e_first, e_first + 3 <= "
+	           "record_doubles)");
+	DX_REQUIRE(K < 3 || (b_first >= 6 && b_first + 3 <= K),
+	           "B's three doubles must lie in the record past the velocity (6 <= b_first, b_first + 3 <= "
+	           "record_doubles)");
+	DX_REQUIRE(K < 3 || b_first >= e_first + 3 || e_first >= b_first + 3,
+	           "E's and B's doubles overlap (e_first and b_first must be at least 3 apart)");
+	DX_REQUIRE(K < 3 || weight_double == -1 ||
+	               (weight_double >= 6 && weight_double < K &&
+	                !(weight_double >= e_first && weight_double < e_first + 3) &&
+	                !(weight_double >= b_first && weight_double < b_first + 3)),
+	           "weight_double must be -1 (q = 1) or a double of the record past the velocity and outside E's and B's "
+	           "three (6 <= weight_double < record_doubles)");
+	DBuf<uint32_t> ofirst;
+	const size_t N_all = particle_mesh_prepare(g, f, K, 0, false, ofirst);
+	const size_t nl = g.n_local;
+	hipStream_t s = g.s_comp;
+	if (!N_all || !nl) return;
+	const size_t N = size_t(var_total(f, nl, s) / (uint64_t(K) * sizeof(double)));  // the local cells' records
+	if (!N) return;
+	particles_boris_kernel<<<grid_for(N, kPB, 1u << 20), kPB, 0, s>>>(reinterpret_cast<double*>(f.data.p), N, K, e_first,
+	                                                                  b_first, weight_double, factor);
 	HIP_CHECK(hipGetLastError());
 	field_written(f);
 	HIP_CHECK(hipStreamSynchronize(s));  // ofirst goes out of scope

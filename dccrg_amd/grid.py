@@ -966,6 +966,37 @@ class Dccrg:
         check(lib().dccrgx_particles_accelerate(self.h, field.id, int(record_doubles), int(first_double), w,
                                                 float(factor)))
 
+    def particles_deposit_moments(self, field, outs, moments, record_doubles, weight=-1, shape="cic",
+                                  per_volume=False, halo=False):
+        """Several moments of the records in one walk of the deposit:
+        outs[j][c] = sum of ((q u) v) W(p, c) with (u, v) = the record's
+        doubles moments[j] (None or -1: 1.0), q = double `weight` (None or -1:
+        1) and W as in particles_deposit, formed once for all moments.
+        (None, None) is the charge, (3, None) q v_x, (3, 4) q v_x v_y; such a
+        charge output has the bits particles_deposit writes.  1 to 16 distinct
+        float64 fields; per_volume, halo and the remote copies as there."""
+        if halo:
+            self.update_copies_of_remote_neighbors()
+        outs, moments = list(outs), [tuple(m) for m in moments]
+        if len(outs) != len(moments) or any(len(m) != 2 for m in moments):
+            raise ValueError("one (u, v) pair of record doubles per output field")
+        w = -1 if weight is None else int(weight)
+        fac = [-1 if x is None else int(x) for m in moments for x in m]
+        ids = (C.c_int * len(outs))(*[f.id for f in outs])
+        check(lib().dccrgx_particles_deposit_moments(self.h, field.id, int(record_doubles), _shape(shape), w,
+                                                     (C.c_int * len(fac))(*fac), ids, len(outs),
+                                                     int(bool(per_volume))))
+
+    def particles_boris(self, field, e_first, b_first, record_doubles, factor, weight=-1):
+        """The Boris kick of every record of a local cell: half the electric
+        kick h E, the rotation about h B, the other half, with E and B the
+        record's doubles e_first .. and b_first .. (past the velocity, not
+        overlapping), h = factor q, q = double `weight` (None or -1: 1);
+        factor = dt / 2m.  include/dccrgx.h states the operations."""
+        w = -1 if weight is None else int(weight)
+        check(lib().dccrgx_particles_boris(self.h, field.id, int(record_doubles), int(e_first), int(b_first), w,
+                                           float(factor)))
+
     def gradient(self, field, out, scale=1.0, region="all", halo=False):
         """out[d] = scale * the d-component of the cell-centred gradient of the
         float64 field `field` in every local cell of `region`; `out` is three

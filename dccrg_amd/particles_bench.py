@@ -26,7 +26,14 @@ volume, rhs = -(rho - mean rho) with torch on the fields' device arrays, a
 Poisson solve of a fixed iteration count, Dccrg.gradient with scale -1, the
 halo, a CIC gather of E, Dccrg.particles_accelerate and the step with
 per-record velocities, each stage timed on its own, and Dccrg.gradient alone
-on the uniform grid and on --adapt's refined one."""
+on the uniform grid and on --adapt's refined one.
+
+--moments measures Dccrg.particles_deposit_moments against the calls it
+replaces, in one run on the same grid: particles_deposit of one double and the
+fused call with 1, 4 (rho, J) and 10 (rho, J, P) moments on a K = 10 pool,
+then on a K = 13 pool (position, velocity, q, E, B) the CIC gather of three
+and of six fields and Dccrg.particles_boris beside particles_accelerate.  The
+calls alternate, each synchronized; median and min - max of the timed ones."""
 from __future__ import annotations
 
 import argparse
@@ -157,6 +164,10 @@ def main(argv=None):
                    help="the electrostatic particle-in-cell cycle stage by stage (deposit, rhs, solve, halo, gradient, "
                         "halo, gather, accelerate, step; K = 10) and dccrgx_gradient alone on the uniform and on "
                         "--adapt's refined grid; writes profiles/particles_bench_pic.json unless --out")
+    p.add_argument("--moments", action="store_true",
+                   help="particles_deposit_moments with 1, 4 and 10 moments beside particles_deposit of one double "
+                        "(K = 10), and the CIC gather of six fields and particles_boris beside particles_accelerate "
+                        "(K = 13), alternating in one run; writes profiles/particles_bench_moments.json unless --out")
     p.add_argument("--pic-iterations", type=int, default=10, help="with --pic: BiCG iterations of a solve (min = max)")
     p.add_argument("--repeats", type=int, default=3)
     p.add_argument("--parent", default=None,
@@ -169,6 +180,8 @@ def main(argv=None):
 
     if a.pic:
         return main_pic(a)
+    if a.moments:
+        return main_moments(a)
     if a.deposit:
         return main_deposit(a)
     if a.adapt:
@@ -611,6 +624,122 @@ def main_pic(a):
     print(txt, flush=True)
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                 "particles_bench_pic.json")
+    with open(out, "w") as f:
+        f.write(txt + "\n")
+
+
+MOMENTS_RHO_J_P = [(None, None), (3, None), (4, None), (5, None),
+                   (3, 3), (3, 4), (3, 5), (4, 4), (4, 5), (5, 5)]
+
+
+def _alternating_ms(g, calls, warmup, steps):
+    """warmup + steps rounds over `calls` (name -> callable) in turn, each call
+    synchronized; per name the median, min, max and every timed run."""
+    t = {k: [] for k in calls}
+    for i in range(warmup + max(steps, 1)):
+        for name, call in calls.items():
+            g.synchronize()
+            t0 = time.perf_counter()
+            call()
+            g.synchronize()
+            if i >= warmup:
+                t[name].append((time.perf_counter() - t0) * 1e3)
+    return {k: dict(ms=float(np.median(v)), min_ms=float(min(v)), max_ms=float(max(v)), runs_ms=v) for k, v in t.items()}
+
+
+def _moments_pool(a, Kp):
+    """base^3 periodic cells with ppc records of Kp doubles: uniform positions,
+    small velocities, q = 1 + 0.1 cos, the rest zero."""
+    import dccrg_amd
+    from dccrg_amd._lib import check, lib
+
+    n = a.base
+    g = dccrg_amd.Dccrg(0, 1, 0).set_initial_length((n, n, n)).set_neighborhood_length(1)
+    g.set_maximum_refinement_level(0).set_periodic(True, True, True).initialize()
+    fld = g.add_variable_field("particles", np.float64, True)
+    ids = g.slot_ids()[: g.n_local]
+    nc = ids.size
+    k = (ids - np.uint64(1)).astype(np.int64)
+    ix = np.stack([k % n, (k // n) % n, k // (n * n)], axis=1)
+    rng = np.random.default_rng(1)
+    rec = np.zeros((nc, a.ppc, Kp))
+    rec[:, :, 0:3] = ix.astype(np.float64)[:, None, :] + rng.random((nc, a.ppc, 3))
+    rec[:, :, 3:6] = 0.2 * (rng.random((nc, a.ppc, 3)) - 0.5)
+    rec[:, :, PIC_Q] = 1 + 0.1 * np.cos(2 * np.pi * rec[:, :, 0] / n)
+    sums = [float(rec[:, :, PIC_Q].sum()), float((rec[:, :, PIC_Q] * rec[:, :, 3]).sum())]
+    rec = rec.reshape(-1)
+    fld.resize(np.full(nc, a.ppc * Kp, np.uint64))
+    check(lib().dccrgx_variable_field_upload(g.h, fld.id, 0, nc, rec.ctypes.data_as(C.c_void_p), rec.nbytes))
+    del rec
+    return g, fld, int(nc), sums
+
+
+def measure_moments(a):
+    g, fld, nc, sums = _moments_pool(a, PIC_K)
+    rho = g.add_field("rho", np.float64, False)
+    outs = [g.add_field(f"m{j}", np.float64, False) for j in range(10)]
+    calls = {"deposit": lambda: g.particles_deposit(fld, rho, PIC_K, PIC_Q, "cic")}
+    for n in (1, 4, 10):
+        calls[f"moments_{n}"] = (lambda n=n: g.particles_deposit_moments(fld, outs[:n], MOMENTS_RHO_J_P[:n], PIC_K,
+                                                                        PIC_Q, "cic"))
+    res = _alternating_ms(g, calls, a.warmup, a.steps)
+    # the ten-moment call ran last: its charge has the deposit's bits, its current sums to the records'
+    assert np.array_equal(rho.get(0, nc).view(np.uint64), outs[0].get(0, nc).view(np.uint64))
+    assert abs(float(outs[0].get(0, nc).sum()) - sums[0]) <= 1e-9 * sums[0]
+    assert abs(float(outs[1].get(0, nc).sum()) - sums[1]) <= 1e-9 * sums[0]
+    g.close()
+    return res, nc
+
+
+def measure_kicks(a):
+    Kb, E0, B0 = 13, 7, 10  # position, velocity, q, E, B
+    g, fld, nc, _ = _moments_pool(a, Kb)
+    fields = [g.add_field(nm, np.float64, False) for nm in ("Ex", "Ey", "Ez", "Bx", "By", "Bz")]
+    for f, v in zip(fields, (1e-3, -2e-3, 5e-4, 0.05, -0.02, 1.0)):
+        f.set(np.full(g.n_slots, v))
+    calls = {"gather_3": lambda: g.particles_gather(fld, fields[:3], E0, Kb, "cic"),
+             "gather_6": lambda: g.particles_gather(fld, fields, E0, Kb, "cic"),
+             "accelerate": lambda: g.particles_accelerate(fld, E0, Kb, 1e-3, PIC_Q),
+             "boris": lambda: g.particles_boris(fld, E0, B0, Kb, 1e-3, PIC_Q)}
+    res = _alternating_ms(g, calls, a.warmup, a.steps)
+    got = fld.get(0, 1)[0].reshape(-1, Kb)
+    assert np.allclose(got[:, 7:13], [1e-3, -2e-3, 5e-4, 0.05, -0.02, 1.0], rtol=1e-12), got[:2]
+    assert np.all(np.abs(got[:, 3:6]) < 0.2)  # the kicks stayed small
+    g.close()
+    return res
+
+
+def main_moments(a):
+    """The fused moments against single deposits, and the Boris kick and the
+    six-field gather against their three-double counterparts."""
+    dep, nc = measure_moments(a)
+    kick = measure_kicks(a)
+    d = dep["deposit"]
+
+    def against(n):
+        m = dep[f"moments_{n}"]
+        return {"ratio_to_one_deposit": m["ms"] / d["ms"], "calls_replaced": n,
+                "max_ms": m["max_ms"], "replaced_min_ms": n * d["min_ms"],
+                "cheaper_beyond_the_spread": bool(m["max_ms"] < n * d["min_ms"])}
+
+    line = {"metric": "particles_deposit_moments", "value": dep["moments_4"]["ms"], "unit": "ms", "n_gpus": 1,
+            "steps": a.steps, "warmup": a.warmup, "higher_is_better": False, "dtype": "fp64",
+            "config": {"workload": f"{a.base}^3 periodic, R = 0, neighborhood 1, {a.ppc} records per cell; CIC, not per "
+                                   f"volume; deposit and moments on a K = {PIC_K} pool (weight double {PIC_Q}; moments "
+                                   "rho, J, P in that order), gathers and kicks on a K = 13 pool (E at 7, B at 10); the "
+                                   "calls of a pool alternate, every call synchronized, median and min - max of the "
+                                   "timed calls", "cells": nc, "particles": nc * a.ppc},
+            "deposit": d, "moments_1": dep["moments_1"], "moments_4": dep["moments_4"], "moments_10": dep["moments_10"],
+            "moments_1_within_deposit_spread": bool(d["min_ms"] <= dep["moments_1"]["ms"] <= d["max_ms"]),
+            "moments_4_against_4_deposits": against(4), "moments_10_against_10_deposits": against(10),
+            "gather_3": kick["gather_3"], "gather_6": kick["gather_6"],
+            "gather_6_over_gather_3": kick["gather_6"]["ms"] / kick["gather_3"]["ms"],
+            "accelerate": kick["accelerate"], "boris": kick["boris"],
+            "boris_over_accelerate": kick["boris"]["ms"] / kick["accelerate"]["ms"]}
+    txt = json.dumps(line)
+    print(txt, flush=True)
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "particles_bench_moments.json")
     with open(out, "w") as f:
         f.write(txt + "\n")
 

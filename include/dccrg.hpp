@@ -1251,6 +1251,34 @@ public:
 		detail::check(dccrgx_particles_accelerate(g_, particles.id(), record_doubles, first_double, weight_double,
 		                                          factor));
 	}
+	// several moments of the records in one walk of the deposit:
+	// out[j][c] = the sum of ((q u) v) W(p, c), (u, v) the record's doubles
+	// moments[j] (-1: 1.0), W formed once for all moments; {-1, -1} is the
+	// charge with particles_deposit's bits, {3, -1} q v_x, {3, 4} q v_x v_y.
+	// 1 to 16 distinct fields.
+	void particles_deposit_moments(const Device_Variable_Field<double>& particles,
+	                               const std::vector<Device_Field<double>>& out,
+	                               const std::vector<std::array<int, 2>>& moments, const int record_doubles,
+	                               const int weight_double = -1, const int shape = 1, const bool per_volume = false) {
+		if (out.size() != moments.size()) throw std::invalid_argument("one pair of record doubles per output field");
+		std::vector<int> id, fac;
+		for (const auto& f : out) id.push_back(f.id());
+		for (const auto& m : moments) {
+			fac.push_back(m[0]);
+			fac.push_back(m[1]);
+		}
+		detail::check(dccrgx_particles_deposit_moments(g_, particles.id(), record_doubles, shape, weight_double,
+		                                               fac.data(), id.data(), int(id.size()), per_volume ? 1 : 0));
+	}
+	// the Boris kick: doubles 3..5 of every record of a local cell take half
+	// the electric kick h E, the rotation about h B and the other half; E at
+	// e_first .., B at b_first .., h = factor q (q = double weight_double,
+	// -1: q = 1), factor = dt / 2m; nothing else of a record is written
+	void particles_boris(const Device_Variable_Field<double>& particles, const int e_first, const int b_first,
+	                     const int record_doubles, const double factor, const int weight_double = -1) {
+		detail::check(dccrgx_particles_boris(g_, particles.id(), record_doubles, e_first, b_first, weight_double,
+		                                     factor));
+	}
 	// out[d] = scale * the d-component of the cell-centred gradient of `in`
 	// over the leaves (dccrgx.h states the operator; nullptr: component not
 	// wanted); in's remote copies are read: update them first

@@ -519,6 +519,49 @@ int dccrgx_particles_gather(dccrgx_grid* g, int var_field, int record_doubles, i
  * [first_double, first_double + 3). */
 int dccrgx_particles_accelerate(dccrgx_grid* g, int var_field, int record_doubles, int first_double,
                                 int weight_double, double factor);
+/* deposit_moments: n moments of the records in one walk of the deposit.  For
+ * every local cell c and j < n, out_fields[j][c] = the sum of m_j(p) W(p, c)
+ * over the records of c and of the distinct leaves of neighbors_of(c), the
+ * copies of remote neighbors included.  W is the deposit's (shape 0: 1 for the
+ * record's own cell; shape 1: the cloud's share), formed once per (record,
+ * receiver) and used by all moments.  m_j(p) = (q_p * u) * v with q_p as in
+ * deposit (record[weight_double], or 1 with -1), u = record[factors[2 j]],
+ * v = record[factors[2 j + 1]]; a factor of -1 stands for 1.0.  q_p * u is one
+ * IEEE product, the product with v the next, then term = m_j * W, then the
+ * sum.  (-1, -1) is the charge, (3, -1) the x-current q v_x, (3, 4) the
+ * pressure component q v_x v_y.  The records are summed in deposit's order
+ * (the same lanes take the same records, the same shuffle tree adds them), so
+ * an output with factors (-1, -1) is bitwise what dccrgx_particles_deposit
+ * writes for the same weight_double, shape and per_volume, wherever it stands
+ * in the list.  per_volume divides each sum by (lx ly) lz as deposit does; the
+ * outputs' remote-copy slots are not written; with no records the local slots
+ * of every output are zeroed; no atomic decides a sum, so two calls on one
+ * state give bitwise equal fields.  DCCRGX_EINVAL: everything deposit refuses
+ * (shape 1 with neighborhood length 0 or a stretched geometry included), n
+ * outside 1 .. 16, a factor that is neither -1 nor in [3, K), an output that
+ * is no fixed 8-byte field, two equal outputs. */
+int dccrgx_particles_deposit_moments(dccrgx_grid* g, int var_field, int record_doubles, int shape, int weight_double,
+                                     const int* factors /* 2 n */, const int* out_fields /* n */, int n,
+                                     int per_volume);
+/* boris: the Boris kick of every record of a local cell.  v = record[3 .. 5],
+ * E = record[e_first ..], B = record[b_first ..] (three doubles each),
+ * h = factor * q with q = record[weight_double], or h = factor with
+ * weight_double == -1; the caller passes factor = dt / 2m.  Each product,
+ * quotient, sum and difference is rounded on its own, in this order (j = 0,
+ * 1, 2):
+ *   hE_j = h * E_j;   vm_j = v_j + hE_j;   t_j = h * B_j
+ *   t2 = (t_0 * t_0 + t_1 * t_1) + t_2 * t_2;   den = 1.0 + t2
+ *   s_j = (2.0 * t_j) / den
+ *   c = vm x t:  c_0 = vm_1 * t_2 - vm_2 * t_1, c_1 = vm_2 * t_0 - vm_0 * t_2,
+ *                c_2 = vm_0 * t_1 - vm_1 * t_0;          vp_j = vm_j + c_j
+ *   d = vp x s   (the same form);                        vq_j = vm_j + d_j
+ *   v_j = vq_j + hE_j
+ * Nothing else of a record and no record of a remote copy is written.
+ * DCCRGX_EINVAL as for accelerate, and unless 6 <= e_first, e_first + 3 <= K,
+ * 6 <= b_first, b_first + 3 <= K, the two ranges do not overlap, and
+ * weight_double is -1 or in [6, K) outside both. */
+int dccrgx_particles_boris(dccrgx_grid* g, int var_field, int record_doubles, int e_first, int b_first,
+                           int weight_double, double factor);
 /* The cell-centred gradient of the fixed fp64 field in_field over the leaves:
  * out_fields[d] (fixed fp64 fields, -1: component not wanted) of every local
  * cell of `region` (DCCRGX_REGION_*; inner then outer writes the bits of all)
