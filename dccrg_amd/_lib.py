@@ -140,6 +140,9 @@ _SIGS = {
                                                    C.c_int, C.c_int]),
     "dccrgx_particles_boris": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
     "dccrgx_gradient": (C.c_int, [vp, C.c_int, P(C.c_int), C.c_double, C.c_int]),
+    "dccrgx_curl": (C.c_int, [vp, P(C.c_int), P(C.c_int), C.c_double, C.c_int, C.c_int]),
+    "dccrgx_divergence": (C.c_int, [vp, P(C.c_int), C.c_int, C.c_double, C.c_int, C.c_int]),
+    "dccrgx_field_axpy": (C.c_int, [vp, C.c_int, C.c_double, C.c_int, C.c_int]),
     "dccrgx_set_send_single_cells": (C.c_int, [vp, C.c_int]),
     "dccrgx_get_send_single_cells": (C.c_int, [vp, P(C.c_int)]),
     "dccrgx_set_field_window": (C.c_int, [vp, C.c_int, sz, sz]),

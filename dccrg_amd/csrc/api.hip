@@ -3457,4 +3457,96 @@ int dccrgx_gradient(dccrgx_grid* gp, int in_field, const int out_fields[3], doub
 	});
 }
 
+namespace {
+const char* const VC_FP64 = "the fields of a curl, divergence or axpy must be fixed-size fields of 8-byte elements (fp64)";
+
+// the three inputs of a curl or divergence (they need not be distinct)
+void vector_inputs(Grid& g, const int in_fields[3], const double* in[3]) {
+	for (int j = 0; j < 3; j++) {
+		DX_REQUIRE(fixed_field(g, in_fields[j]).elem == 8, VC_FP64);
+		in[j] = reinterpret_cast<const double*>(field(g, in_fields[j]).data.p);
+	}
+}
+}  // namespace
+
+// the curl of three fp64 cell fields over the face table (curl_kernel,
+// poisson_kernels.hip); every check precedes the first write
+int dccrgx_curl(dccrgx_grid* gp, const int in_fields[3], const int out_fields[3], double scale, int accumulate,
+                int region) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		DX_REQUIRE(g.initialized, "grid not initialized");
+		DX_REQUIRE(in_fields && out_fields, "null pointer");
+		const double* in[3];
+		vector_inputs(g, in_fields, in);
+		int wanted = 0;
+		for (int k = 0; k < 3; k++) {
+			if (out_fields[k] == -1) continue;
+			DX_REQUIRE(fixed_field(g, out_fields[k]).elem == 8, VC_FP64);
+			for (int j = 0; j < 3; j++) DX_REQUIRE(out_fields[k] != in_fields[j], "a curl output is an input field");
+			for (int e = 0; e < k; e++) DX_REQUIRE(out_fields[e] != out_fields[k], "two curl outputs are one field");
+			wanted++;
+		}
+		DX_REQUIRE(wanted, "no curl output wanted (all three are -1)");
+		size_t s0, s1;
+		region_range(g, region, s0, s1);
+		ensure_face(g);
+		double* out[3] = {nullptr, nullptr, nullptr};
+		for (int k = 0; k < 3; k++) {
+			if (out_fields[k] == -1) continue;
+			Field& F = field(g, out_fields[k]);
+			field_written(F);
+			out[k] = reinterpret_cast<double*>(F.data.p);
+		}
+		k_time_begin(g);
+		k_curl(g.m, g.l0, stretched_view(g), g.slot_ids.p, g.slot_lvl.p, g.face_ell.p, g.face_fine.p, in, out, scale,
+		       accumulate != 0, s0, s1, g.s_comp);
+		k_time_end(g);
+		return 0;
+	});
+}
+
+// the divergence of three fp64 cell fields (divergence_kernel)
+int dccrgx_divergence(dccrgx_grid* gp, const int in_fields[3], int out_field, double scale, int accumulate,
+                      int region) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		DX_REQUIRE(g.initialized, "grid not initialized");
+		DX_REQUIRE(in_fields, "null pointer");
+		const double* in[3];
+		vector_inputs(g, in_fields, in);
+		DX_REQUIRE(fixed_field(g, out_field).elem == 8, VC_FP64);
+		for (int j = 0; j < 3; j++) DX_REQUIRE(out_field != in_fields[j], "the divergence's output is an input field");
+		size_t s0, s1;
+		region_range(g, region, s0, s1);
+		ensure_face(g);
+		Field& F = field(g, out_field);
+		field_written(F);
+		k_time_begin(g);
+		k_divergence(g.m, g.l0, stretched_view(g), g.slot_ids.p, g.slot_lvl.p, g.face_ell.p, g.face_fine.p, in,
+		             reinterpret_cast<double*>(F.data.p), scale, accumulate != 0, s0, s1, g.s_comp);
+		k_time_end(g);
+		return 0;
+	});
+}
+
+// y = y + (a * x) over the local slots of a region (field_axpy_kernel)
+int dccrgx_field_axpy(dccrgx_grid* gp, int y_field, double a, int x_field, int region) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		DX_REQUIRE(g.initialized, "grid not initialized");
+		DX_REQUIRE(fixed_field(g, y_field).elem == 8 && fixed_field(g, x_field).elem == 8, VC_FP64);
+		DX_REQUIRE(x_field != y_field, "the axpy's x and y are one field");
+		size_t s0, s1;
+		region_range(g, region, s0, s1);
+		Field& Y = field(g, y_field);
+		field_written(Y);
+		k_time_begin(g);
+		k_field_axpy(reinterpret_cast<double*>(Y.data.p), a, reinterpret_cast<const double*>(field(g, x_field).data.p),
+		             s0, s1, g.s_comp);
+		k_time_end(g);
+		return 0;
+	});
+}
+
 }  // extern "C"

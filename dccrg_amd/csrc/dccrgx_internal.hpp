@@ -1226,6 +1226,19 @@ void k_po_scalar(const double* all, int P, int k, PoScalars* st, const PoParams&
 void k_gradient(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
                 const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine, const double* in,
                 double* const out[3], double scale, size_t s0, size_t s1, hipStream_t s);
+// dccrgx_curl over the local slots [s0, s1): out[k] (nullptr: not wanted) = or
+// += scale * the k-component of the curl of the three fields `in`, whose
+// derivatives are k_gradient's bit for bit
+void k_curl(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
+            const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine, const double* const in[3],
+            double* const out[3], double scale, bool accumulate, size_t s0, size_t s1, hipStream_t s);
+// dccrgx_divergence likewise: out = or += scale * ((D_0 in[0] + D_1 in[1]) + D_2 in[2])
+void k_divergence(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
+                  const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine,
+                  const double* const in[3], double* out, double scale, bool accumulate, size_t s0, size_t s1,
+                  hipStream_t s);
+// dccrgx_field_axpy: y = y + (a * x) over the slots [s0, s1)
+void k_field_axpy(double* y, double a, const double* x, size_t s0, size_t s1, hipStream_t s);
 
 }  // namespace dccrgx
 

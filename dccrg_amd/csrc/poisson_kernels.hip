@@ -498,31 +498,14 @@ inline unsigned po_blocks(size_t n) {
 	return unsigned(b ? b : 8);
 }
 
-// dccrgx_gradient (dccrgx.h): the cell-centred gradient of `in` over the
-// unfiltered face table for the local slots [s0, s1), the first-derivative
-// counterpart of set_scaling_factor's second derivative: the same centre
-// distances (own half length + the neighbor's), the same three-point stencil
-// per dimension.  The Poisson classification is not consulted.
-// A neighbor's length along the face's dimension needs its level only
-// (slot_lvl, one byte per slot, made with the face table): neighbors differ by
-// at most one level, the four finer cells of a face are one level up, and
-// under a stretched geometry the neighbor's level-0 cell along d follows from
-// this cell's own indices (the index just past its upper face or just below
-// its lower one, wrapped), so no neighbor id is decoded.
-template <bool STRETCHED>
-__global__ __launch_bounds__(BS) void gradient_kernel(MapCtx m, double l0x, double l0y, double l0z, StretchedView G,
-                                                      const uint64_t* __restrict__ slot_ids,
-                                                      const uint8_t* __restrict__ slot_lvl,
-                                                      const int32_t* __restrict__ face_ell,
-                                                      const int32_t* __restrict__ face_fine,
-                                                      const double* __restrict__ in, double* __restrict__ ox,
-                                                      double* __restrict__ oy, double* __restrict__ oz, double scale,
-                                                      size_t s0, size_t s1) {
-#pragma clang fp contract(off)
-	const size_t s = s0 + size_t(xcd_block()) * BS + threadIdx.x;
-	if (s >= s1) return;
-	// the six face entries of the row (24 bytes, 8-byte aligned) together
-	int32_t ev[6];
+// ---- the first-derivative stencil over the face table ------------------------
+// What gradient_kernel, curl_kernel and divergence_kernel share, so that the
+// derivative of a field along a dimension has the same bits in all three
+// (dccrgx.h: D_d(F)[c]): the face row, a side's value and level, the lengths,
+// a dimension's coefficients and the three-point derivative.
+
+// the six face entries of row s (24 bytes, 8-byte aligned) together
+__device__ __forceinline__ void face_row(const int32_t* __restrict__ face_ell, size_t s, int32_t (&ev)[6]) {
 	const int2* row = reinterpret_cast<const int2*>(face_ell + 6 * s);
 #pragma unroll
 	for (int k = 0; k < 3; k++) {
@@ -530,28 +513,38 @@ __global__ __launch_bounds__(BS) void gradient_kernel(MapCtx m, double l0x, doub
 		ev[2 * k] = r.x;
 		ev[2 * k + 1] = r.y;
 	}
-	const int lvl = slot_lvl[s] & 31;
-	const double vc = in[s];
-	// the six neighbor values and levels, gathered before the ordered arithmetic
-	double v[6];
-	int nl[6];
-#pragma unroll
-	for (int dir = 0; dir < 6; dir++) {
-		const int32_t e = ev[dir];
-		v[dir] = 0.0;
-		nl[dir] = lvl;
-		if (e >= 0) {
-			v[dir] = in[e];
-			nl[dir] = slot_lvl[e] & 31;
-		} else if (e < -1) {
-			const int32_t* f = face_fine + 4 * size_t(-2 - e);
-			const double a0 = in[f[0]], a1 = in[f[1]], a2 = in[f[2]], a3 = in[f[3]];
-			v[dir] = ((a0 + a1) + (a2 + a3)) / 4.0;
-			nl[dir] = lvl + 1;
-		}
+}
+
+// the value of `in` across the face entry e: the neighbor's, the mean of the
+// four finer cells' in face_fine order, or 0.0 without a neighbor
+__device__ __forceinline__ double face_value(const double* __restrict__ in, const int32_t* __restrict__ face_fine,
+                                             int32_t e) {
+#pragma clang fp contract(off)
+	double v = 0.0;
+	if (e >= 0) {
+		v = in[e];
+	} else if (e < -1) {
+		const int32_t* f = face_fine + 4 * size_t(-2 - e);
+		const double a0 = in[f[0]], a1 = in[f[1]], a2 = in[f[2]], a3 = in[f[3]];
+		v = ((a0 + a1) + (a2 + a3)) / 4.0;
 	}
-	// lengths along d of the cell and of its two neighbors
-	double lc[3], ln[6];
+	return v;
+}
+
+// the level of the cell(s) across the face entry e of a cell of level lvl
+__device__ __forceinline__ int face_level(const uint8_t* __restrict__ slot_lvl, int32_t e, int lvl) {
+	if (e >= 0) return slot_lvl[e] & 31;
+	return e < -1 ? lvl + 1 : lvl;
+}
+
+// lengths along d of the cell of slot s (lc) and of its two neighbors (ln),
+// whose levels are nl
+template <bool STRETCHED>
+__device__ __forceinline__ void stencil_lengths(const MapCtx& m, double l0x, double l0y, double l0z,
+                                                const StretchedView& G, const uint64_t* __restrict__ slot_ids,
+                                                size_t s, int lvl, const int (&nl)[6], double (&lc)[3],
+                                                double (&ln)[6]) {
+#pragma clang fp contract(off)
 	if constexpr (STRETCHED) {
 		uint64_t ind[3] = {0, 0, 0};
 		map_indices(m, slot_ids[s], ind[0], ind[1], ind[2]);
@@ -576,26 +569,220 @@ __global__ __launch_bounds__(BS) void gradient_kernel(MapCtx m, double l0x, doub
 			ln[2 * d + 1] = l0[d] * (1.0 / double(uint64_t(1) << nl[2 * d + 1]));
 		}
 	}
+}
+
+// a dimension's coefficients: with both sides a and b of the three-point
+// stencil; with one side the centre distance h in `a` (the contract divides by
+// it, so the divisor is kept and not its reciprocal)
+constexpr int ST_NONE = 0, ST_BOTH = 1, ST_POS = 2, ST_NEG = 3;
+struct StencilDim {
+	int sides;
+	double a, b;
+};
+__device__ __forceinline__ StencilDim stencil_dim(double lc, double ln_neg, double ln_pos, int32_t e_neg,
+                                                  int32_t e_pos) {
+#pragma clang fp contract(off)
+	const double hc = lc / 2.0;
+	const bool has_neg = e_neg != -1, has_pos = e_pos != -1;
+	const double h_neg = hc + ln_neg / 2.0, h_pos = hc + ln_pos / 2.0;
+	StencilDim k{ST_NONE, 0.0, 0.0};
+	if (has_neg && has_pos) {
+		const double tot = h_pos + h_neg;
+		k.sides = ST_BOTH;
+		k.a = h_neg / (h_pos * tot);
+		k.b = h_pos / (h_neg * tot);
+	} else if (has_pos) {
+		k.sides = ST_POS;
+		k.a = h_pos;
+	} else if (has_neg) {
+		k.sides = ST_NEG;
+		k.a = h_neg;
+	}
+	return k;
+}
+
+// the derivative along the dimension of k from the values on its two sides
+// and the cell's own: `grad` of dccrgx_gradient's contract, before the scaling
+__device__ __forceinline__ double stencil_derivative(const StencilDim& k, double v_neg, double vc, double v_pos) {
+#pragma clang fp contract(off)
+	const double dp = v_pos - vc, dn = vc - v_neg;
+	double grad = 0.0;
+	if (k.sides == ST_BOTH) grad = k.a * dp + k.b * dn;
+	else if (k.sides == ST_POS) grad = dp / k.a;
+	else if (k.sides == ST_NEG) grad = dn / k.a;
+	return grad;
+}
+
+// dccrgx_gradient (dccrgx.h): the cell-centred gradient of `in` over the
+// unfiltered face table for the local slots [s0, s1), the first-derivative
+// counterpart of set_scaling_factor's second derivative: the same centre
+// distances (own half length + the neighbor's), the same three-point stencil
+// per dimension.  The Poisson classification is not consulted.
+// A neighbor's length along the face's dimension needs its level only
+// (slot_lvl, one byte per slot, made with the face table): neighbors differ by
+// at most one level, the four finer cells of a face are one level up, and
+// under a stretched geometry the neighbor's level-0 cell along d follows from
+// this cell's own indices (the index just past its upper face or just below
+// its lower one, wrapped), so no neighbor id is decoded.
+template <bool STRETCHED>
+__global__ __launch_bounds__(BS) void gradient_kernel(MapCtx m, double l0x, double l0y, double l0z, StretchedView G,
+                                                      const uint64_t* __restrict__ slot_ids,
+                                                      const uint8_t* __restrict__ slot_lvl,
+                                                      const int32_t* __restrict__ face_ell,
+                                                      const int32_t* __restrict__ face_fine,
+                                                      const double* __restrict__ in, double* __restrict__ ox,
+                                                      double* __restrict__ oy, double* __restrict__ oz, double scale,
+                                                      size_t s0, size_t s1) {
+#pragma clang fp contract(off)
+	const size_t s = s0 + size_t(xcd_block()) * BS + threadIdx.x;
+	if (s >= s1) return;
+	int32_t ev[6];
+	face_row(face_ell, s, ev);
+	const int lvl = slot_lvl[s] & 31;
+	const double vc = in[s];
+	// the six neighbor values and levels, gathered before the ordered arithmetic
+	double v[6];
+	int nl[6];
+#pragma unroll
+	for (int dir = 0; dir < 6; dir++) {
+		v[dir] = face_value(in, face_fine, ev[dir]);
+		nl[dir] = face_level(slot_lvl, ev[dir], lvl);
+	}
+	double lc[3], ln[6];
+	stencil_lengths<STRETCHED>(m, l0x, l0y, l0z, G, slot_ids, s, lvl, nl, lc, ln);
 	double* const out[3] = {ox, oy, oz};
 #pragma unroll
 	for (int d = 0; d < 3; d++) {
 		if (!out[d]) continue;
-		const double hc = lc[d] / 2.0;
-		const bool has_neg = ev[2 * d] != -1, has_pos = ev[2 * d + 1] != -1;
-		const double h_neg = hc + ln[2 * d] / 2.0, h_pos = hc + ln[2 * d + 1] / 2.0;
-		const double dp = v[2 * d + 1] - vc, dn = vc - v[2 * d];
-		double grad = 0.0;
-		if (has_neg && has_pos) {
-			const double tot = h_pos + h_neg;
-			const double a = h_neg / (h_pos * tot);
-			const double b = h_pos / (h_neg * tot);
-			grad = a * dp + b * dn;
-		} else if (has_pos) {
-			grad = dp / h_pos;
-		} else if (has_neg) {
-			grad = dn / h_neg;
+		const StencilDim k = stencil_dim(lc[d], ln[2 * d], ln[2 * d + 1], ev[2 * d], ev[2 * d + 1]);
+		out[d][s] = scale * stencil_derivative(k, v[2 * d], vc, v[2 * d + 1]);
+	}
+}
+
+// dccrgx_curl / dccrgx_divergence (dccrgx.h) of the three fields f0, f1, f2 for
+// the local slots [s0, s1).  The face row, the seven levels, the lengths and
+// the three dimensions' coefficients are formed once per cell and serve all
+// three fields.  The field pointers are kernel arguments and every array of
+// them is indexed by unrolled constants only, so they stay in SGPRs.
+// The value of field j across the faces of dimension d is wanted by the curl
+// component 3 - j - d alone (d != j): 12 gathered values when all three
+// components are wanted; the divergence takes the 6 with d == j.
+template <bool STRETCHED, bool ACCUMULATE>
+__global__ __launch_bounds__(BS) void curl_kernel(MapCtx m, double l0x, double l0y, double l0z, StretchedView G,
+                                                  const uint64_t* __restrict__ slot_ids,
+                                                  const uint8_t* __restrict__ slot_lvl,
+                                                  const int32_t* __restrict__ face_ell,
+                                                  const int32_t* __restrict__ face_fine, const double* f0,
+                                                  const double* f1, const double* f2, double* ox, double* oy,
+                                                  double* oz, double scale, size_t s0, size_t s1) {
+#pragma clang fp contract(off)
+	const size_t s = s0 + size_t(xcd_block()) * BS + threadIdx.x;
+	if (s >= s1) return;
+	int32_t ev[6];
+	face_row(face_ell, s, ev);
+	const int lvl = slot_lvl[s] & 31;
+	const double* const F[3] = {f0, f1, f2};
+	double* const out[3] = {ox, oy, oz};
+	// the gathers first: the levels, then per wanted component its four values
+	int nl[6];
+#pragma unroll
+	for (int dir = 0; dir < 6; dir++) nl[dir] = face_level(slot_lvl, ev[dir], lvl);
+	double vc[3], v[3][6], prev[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+	for (int j = 0; j < 3; j++) {
+		vc[j] = F[j][s];
+		if constexpr (ACCUMULATE)
+			if (out[j]) prev[j] = out[j][s];
+#pragma unroll
+		for (int d = 0; d < 3; d++) {
+			if (d == j) continue;
+			if (!out[3 - j - d]) continue;
+			v[j][2 * d] = face_value(F[j], face_fine, ev[2 * d]);
+			v[j][2 * d + 1] = face_value(F[j], face_fine, ev[2 * d + 1]);
 		}
-		out[d][s] = scale * grad;
+	}
+	double lc[3], ln[6];
+	stencil_lengths<STRETCHED>(m, l0x, l0y, l0z, G, slot_ids, s, lvl, nl, lc, ln);
+	StencilDim k[3];
+#pragma unroll
+	for (int d = 0; d < 3; d++) k[d] = stencil_dim(lc[d], ln[2 * d], ln[2 * d + 1], ev[2 * d], ev[2 * d + 1]);
+#pragma unroll
+	for (int c = 0; c < 3; c++) {
+		if (!out[c]) continue;
+		constexpr int nxt[3] = {1, 2, 0};
+		const int d1 = nxt[c], d2 = nxt[d1];  // r_c = D_d1(F_d2) - D_d2(F_d1)
+		const double p = stencil_derivative(k[d1], v[d2][2 * d1], vc[d2], v[d2][2 * d1 + 1]);
+		const double q = stencil_derivative(k[d2], v[d1][2 * d2], vc[d1], v[d1][2 * d2 + 1]);
+		const double r = p - q;
+		const double t = scale * r;
+		if constexpr (ACCUMULATE) out[c][s] = prev[c] + t;
+		else out[c][s] = t;
+	}
+}
+
+template <bool STRETCHED, bool ACCUMULATE>
+__global__ __launch_bounds__(BS) void divergence_kernel(MapCtx m, double l0x, double l0y, double l0z, StretchedView G,
+                                                        const uint64_t* __restrict__ slot_ids,
+                                                        const uint8_t* __restrict__ slot_lvl,
+                                                        const int32_t* __restrict__ face_ell,
+                                                        const int32_t* __restrict__ face_fine, const double* f0,
+                                                        const double* f1, const double* f2, double* out, double scale,
+                                                        size_t s0, size_t s1) {
+#pragma clang fp contract(off)
+	const size_t s = s0 + size_t(xcd_block()) * BS + threadIdx.x;
+	if (s >= s1) return;
+	int32_t ev[6];
+	face_row(face_ell, s, ev);
+	const int lvl = slot_lvl[s] & 31;
+	const double* const F[3] = {f0, f1, f2};
+	int nl[6];
+	double vc[3], v[6];
+#pragma unroll
+	for (int d = 0; d < 3; d++) {
+		nl[2 * d] = face_level(slot_lvl, ev[2 * d], lvl);
+		nl[2 * d + 1] = face_level(slot_lvl, ev[2 * d + 1], lvl);
+		vc[d] = F[d][s];
+		v[2 * d] = face_value(F[d], face_fine, ev[2 * d]);
+		v[2 * d + 1] = face_value(F[d], face_fine, ev[2 * d + 1]);
+	}
+	double lc[3], ln[6];
+	stencil_lengths<STRETCHED>(m, l0x, l0y, l0z, G, slot_ids, s, lvl, nl, lc, ln);
+	double D[3];
+#pragma unroll
+	for (int d = 0; d < 3; d++) {
+		const StencilDim k = stencil_dim(lc[d], ln[2 * d], ln[2 * d + 1], ev[2 * d], ev[2 * d + 1]);
+		D[d] = stencil_derivative(k, v[2 * d], vc[d], v[2 * d + 1]);
+	}
+	const double r = (D[0] + D[1]) + D[2];
+	const double t = scale * r;
+	if constexpr (ACCUMULATE) out[s] = out[s] + t;
+	else out[s] = t;
+}
+
+// dccrgx_field_axpy: y = y + (a * x) over the slots [s0, s1), the product
+// rounded before the sum.  A field's array starts 256-byte aligned (DBuf), so
+// pairs from the first even slot on go as 16-byte loads and stores, a leading
+// odd slot and a trailing single one on their own.
+__global__ __launch_bounds__(BS) void field_axpy_kernel(double* __restrict__ y, const double* __restrict__ x, double a,
+                                                        size_t s0, size_t s1) {
+#pragma clang fp contract(off)
+	const size_t t = size_t(blockIdx.x) * BS + threadIdx.x;
+	const size_t b = (s0 + 1) & ~size_t(1);
+	const size_t i = b + 2 * t;
+	if (i + 1 < s1) {
+		double2 yv = *reinterpret_cast<const double2*>(y + i);
+		const double2 xv = *reinterpret_cast<const double2*>(x + i);
+		const double p0 = a * xv.x, p1 = a * xv.y;
+		yv.x = yv.x + p0;
+		yv.y = yv.y + p1;
+		*reinterpret_cast<double2*>(y + i) = yv;
+	} else if (i < s1) {
+		const double p = a * x[i];
+		y[i] = y[i] + p;
+	}
+	if (t == 0 && b != s0) {  // (s0 < s1: the launcher starts nothing for an empty range)
+		const double p = a * x[s0];
+		y[s0] = y[s0] + p;
 	}
 }
 
@@ -612,6 +799,52 @@ void k_gradient(const MapCtx& m, const double l0[3], const StretchedView& G, con
 	else
 		gradient_kernel<false><<<nb, BS, 0, s>>>(m, l0[0], l0[1], l0[2], G, slot_ids, slot_lvl, face_ell, face_fine, in,
 		                                         out[0], out[1], out[2], scale, s0, s1);
+	HIP_CHECK(hipGetLastError());
+}
+
+void k_curl(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
+            const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine, const double* const in[3],
+            double* const out[3], double scale, bool accumulate, size_t s0, size_t s1, hipStream_t s) {
+	if (s1 <= s0) return;
+	const unsigned nb = po_blocks(s1 - s0);
+	auto launch = [&](auto kernel) {
+		kernel<<<nb, BS, 0, s>>>(m, l0[0], l0[1], l0[2], G, slot_ids, slot_lvl, face_ell, face_fine, in[0], in[1], in[2],
+		                         out[0], out[1], out[2], scale, s0, s1);
+	};
+	if (G.c) {
+		if (accumulate) launch(curl_kernel<true, true>);
+		else launch(curl_kernel<true, false>);
+	} else {
+		if (accumulate) launch(curl_kernel<false, true>);
+		else launch(curl_kernel<false, false>);
+	}
+	HIP_CHECK(hipGetLastError());
+}
+
+void k_divergence(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
+                  const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine,
+                  const double* const in[3], double* out, double scale, bool accumulate, size_t s0, size_t s1,
+                  hipStream_t s) {
+	if (s1 <= s0) return;
+	const unsigned nb = po_blocks(s1 - s0);
+	auto launch = [&](auto kernel) {
+		kernel<<<nb, BS, 0, s>>>(m, l0[0], l0[1], l0[2], G, slot_ids, slot_lvl, face_ell, face_fine, in[0], in[1], in[2],
+		                         out, scale, s0, s1);
+	};
+	if (G.c) {
+		if (accumulate) launch(divergence_kernel<true, true>);
+		else launch(divergence_kernel<true, false>);
+	} else {
+		if (accumulate) launch(divergence_kernel<false, true>);
+		else launch(divergence_kernel<false, false>);
+	}
+	HIP_CHECK(hipGetLastError());
+}
+
+void k_field_axpy(double* y, double a, const double* x, size_t s0, size_t s1, hipStream_t s) {
+	if (s1 <= s0) return;
+	const size_t pairs = (s1 - s0) / 2 + 1;  // from the first even slot on, a trailing single one included
+	field_axpy_kernel<<<unsigned((pairs + BS - 1) / BS), BS, 0, s>>>(y, x, a, s0, s1);
 	HIP_CHECK(hipGetLastError());
 }
 

@@ -1011,6 +1011,39 @@ class Dccrg:
         ids = (C.c_int * 3)(*[-1 if f is None else f.id for f in out])
         check(lib().dccrgx_gradient(self.h, field.id, ids, float(scale), REGION[region]))
 
+    def curl(self, fields, out, scale=1.0, accumulate=False, region="all", halo=False):
+        """out[k] = (accumulate: out[k] +) scale * the k-component of the curl
+        of the three float64 Fields `fields` in every local cell of `region`;
+        `out` is three float64 Fields or Nones (component not wanted).  The
+        derivatives are gradient's, bit for bit.  The remote copies of
+        `fields` are read (halo=True refreshes them first), those of the
+        outputs are not written.  include/dccrgx.h states the operations."""
+        if halo:
+            self.update_copies_of_remote_neighbors()
+        fields, out = list(fields), list(out)
+        if len(fields) != 3 or len(out) != 3:
+            raise ValueError("fields must hold three Fields, out three Fields or Nones")
+        fin = (C.c_int * 3)(*[f.id for f in fields])
+        ids = (C.c_int * 3)(*[-1 if f is None else f.id for f in out])
+        check(lib().dccrgx_curl(self.h, fin, ids, float(scale), int(bool(accumulate)), REGION[region]))
+
+    def divergence(self, fields, out, scale=1.0, accumulate=False, region="all", halo=False):
+        """out = (accumulate: out +) scale * the divergence of the three
+        float64 Fields `fields` in every local cell of `region`: the sum of
+        gradient's d-derivative of fields[d].  Remote copies as for curl."""
+        if halo:
+            self.update_copies_of_remote_neighbors()
+        fields = list(fields)
+        if len(fields) != 3:
+            raise ValueError("fields must hold three Fields")
+        fin = (C.c_int * 3)(*[f.id for f in fields])
+        check(lib().dccrgx_divergence(self.h, fin, out.id, float(scale), int(bool(accumulate)), REGION[region]))
+
+    def field_axpy(self, y, a, x, region="all"):
+        """y = y + (a * x) in every local cell of `region`, the product rounded
+        before the sum; two distinct float64 Fields."""
+        check(lib().dccrgx_field_axpy(self.h, y.id, float(a), x.id, REGION[region]))
+
     # ---- built-in sweeps ------------------------------------------------------------
     def gol_step(self, state: Field, region="all"):
         check(lib().dccrgx_gol_step(self.h, state.id, REGION[region]))

@@ -33,7 +33,12 @@ replaces, in one run on the same grid: particles_deposit of one double and the
 fused call with 1, 4 (rho, J) and 10 (rho, J, P) moments on a K = 10 pool,
 then on a K = 13 pool (position, velocity, q, E, B) the CIC gather of three
 and of six fields and Dccrg.particles_boris beside particles_accelerate.  The
-calls alternate, each synchronized; median and min - max of the timed ones."""
+calls alternate, each synchronized; median and min - max of the timed ones.
+
+--curl measures Dccrg.curl (plain and accumulating), Dccrg.divergence,
+Dccrg.gradient and Dccrg.field_axpy beside the curl a caller composed before
+them from three gradient calls into six scratch fields and three axpys, the
+six alternating in one run on --pic's two gradient grids."""
 from __future__ import annotations
 
 import argparse
@@ -168,6 +173,10 @@ def main(argv=None):
                    help="particles_deposit_moments with 1, 4 and 10 moments beside particles_deposit of one double "
                         "(K = 10), and the CIC gather of six fields and particles_boris beside particles_accelerate "
                         "(K = 13), alternating in one run; writes profiles/particles_bench_moments.json unless --out")
+    p.add_argument("--curl", action="store_true",
+                   help="dccrgx_curl (plain and accumulating), dccrgx_divergence, dccrgx_gradient, dccrgx_field_axpy and "
+                        "the curl composed from three gradients and three axpys, alternating in one run on the uniform "
+                        "and on --adapt's refined grid; writes profiles/particles_bench_curl.json unless --out")
     p.add_argument("--pic-iterations", type=int, default=10, help="with --pic: BiCG iterations of a solve (min = max)")
     p.add_argument("--repeats", type=int, default=3)
     p.add_argument("--parent", default=None,
@@ -178,6 +187,8 @@ def main(argv=None):
 
     import torch  # noqa: F401  (one HIP runtime for the process)
 
+    if a.curl:
+        return main_curl(a)
     if a.pic:
         return main_pic(a)
     if a.moments:
@@ -740,6 +751,118 @@ def main_moments(a):
     print(txt, flush=True)
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                 "particles_bench_moments.json")
+    with open(out, "w") as f:
+        f.write(txt + "\n")
+
+
+# curl_kernel per local cell: three inputs 24 B + face row 24 B + three outputs 24 B (read too when accumulating);
+# divergence_kernel: 24 + 24 + 8; field_axpy_kernel: x and y read, y written; the composition the calls replace:
+# three gradients of two outputs each (8 + 24 + 16) and three axpys
+CURL_MIN_BYTES, CURL_ACC_BYTES, DIVERGENCE_MIN_BYTES, AXPY_BYTES = 72, 96, 56, 24
+COMPOSED_CURL_BYTES = 3 * (8 + 24 + 16) + 3 * AXPY_BYTES
+CURL_NEXT = (1, 2, 0)
+
+
+def measure_curl(a, refined):
+    """dccrgx_curl (plain and accumulating), dccrgx_divergence, dccrgx_gradient
+    and dccrgx_field_axpy, and the curl composed from the calls there were
+    before them (three gradients into six scratch fields, three axpys), on
+    measure_gradient's grid; the calls alternate in one run, each synchronized."""
+    import dccrg_amd
+
+    n = a.base
+    g = dccrg_amd.Dccrg(0, 1, 0).set_initial_length((n, n, n)).set_neighborhood_length(1)
+    g.set_maximum_refinement_level(1 if refined else 0).set_periodic(True, True, True).initialize()
+    if refined:
+        _refine_slab(g, n)
+    nc = int(g.n_local)
+    rng = np.random.default_rng(2)
+    F = [g.add_field(nm, np.float64, False) for nm in ("Fx", "Fy", "Fz")]
+    for f in F:
+        f.set(rng.random(g.n_slots))
+    out = [g.add_field(nm, np.float64, False) for nm in ("Cx", "Cy", "Cz")]
+    acc = [g.add_field(nm, np.float64, False) for nm in ("Bx", "By", "Bz")]
+    for f in acc:
+        f.set(np.zeros(g.n_slots))
+    div = g.add_field("div", np.float64, False)
+    grad = [g.add_field(nm, np.float64, False) for nm in ("Gx", "Gy", "Gz")]
+    # P[k] = D_d1(F_d2), Q[k] = D_d2(F_d1) with (k, d1, d2) cyclic: the gradient of F_j fills P[j + 1] and Q[j + 2]
+    P = [g.add_field(f"P{k}", np.float64, False) for k in range(3)]
+    Q = [g.add_field(f"Q{k}", np.float64, False) for k in range(3)]
+    y = g.add_field("y", np.float64, False)
+    y.set(np.zeros(g.n_slots))
+
+    def composed():
+        for j in range(3):
+            o = [None, None, None]
+            k_p, k_q = CURL_NEXT[j], CURL_NEXT[CURL_NEXT[j]]  # j = d2 of k_p, j = d1 of k_q
+            o[CURL_NEXT[k_p]] = P[k_p]
+            o[CURL_NEXT[CURL_NEXT[k_q]]] = Q[k_q]
+            g.gradient(F[j], o, 1.0)
+        for k in range(3):
+            g.field_axpy(P[k], -1.0, Q[k])
+
+    calls = {"curl": lambda: g.curl(F, out, 1.0),
+             "curl_accumulate": lambda: g.curl(F, acc, -1e-3, True),
+             "divergence": lambda: g.divergence(F, div, 1.0),
+             "gradient": lambda: g.gradient(F[0], grad, -1.0),
+             "field_axpy": lambda: g.field_axpy(y, 1e-3, F[0]),
+             "composed_curl": composed}
+    res = _alternating_ms(g, calls, a.warmup, a.steps)
+    # the composition's result is the fused call's, bit for bit
+    for k in range(3):
+        assert np.array_equal(out[k].get(0, nc).view(np.uint64), P[k].get(0, nc).view(np.uint64)), k
+    # the fused kernels between device events (dccrgx_kernel_timing), as measure_gradient takes the gradient's
+    for name in ("curl", "curl_accumulate", "divergence"):
+        g.kernel_timing(1)
+        for _ in range(max(a.steps, 1)):
+            calls[name]()
+        g.synchronize()
+        kms, kn = g.kernel_timing(0)
+        res[name]["kernel_ms"] = kms / max(kn, 1)
+        res[name]["kernel_launches"] = int(kn)
+    g.close()
+
+    def roofline(t, b):
+        ach = nc * b / (t / 1e3) / 1e9
+        return {"bound": "hbm", "bytes_per_cell": b, "achieved": ach, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                "frac": ach / PEAK_HBM_GBS}
+
+    for name, b in (("curl", CURL_MIN_BYTES), ("curl_accumulate", CURL_ACC_BYTES), ("divergence", DIVERGENCE_MIN_BYTES),
+                    ("gradient", GRADIENT_MIN_BYTES), ("field_axpy", AXPY_BYTES), ("composed_curl", COMPOSED_CURL_BYTES)):
+        res[name]["roofline"] = roofline(res[name]["ms"], b)
+        if "kernel_ms" in res[name]:
+            res[name]["roofline_kernel"] = roofline(res[name]["kernel_ms"], b)
+    res["cells"] = nc
+    res["curl_over_composed_curl"] = res["curl"]["ms"] / res["composed_curl"]["ms"]
+    res["curl_over_gradient"] = res["curl"]["ms"] / res["gradient"]["ms"]
+    met = bool(res["curl"]["max_ms"] < res["composed_curl"]["min_ms"])
+    res["fused_max_below_composed_min"] = {"curl_max_ms": res["curl"]["max_ms"],
+                                           "composed_min_ms": res["composed_curl"]["min_ms"],
+                                           "verdict": "met" if met else "not met"}
+    return res
+
+
+def main_curl(a):
+    """The fused curl and divergence against the gradient and against the
+    composition from gradients and axpys, on the uniform and the refined grid."""
+    uni = measure_curl(a, False)
+    ref = measure_curl(a, True)
+    line = {"metric": "curl", "value": uni["curl"]["ms"], "unit": "ms", "n_gpus": 1, "steps": a.steps,
+            "warmup": a.warmup, "higher_is_better": False, "dtype": "fp64",
+            "config": {"workload": f"{a.base}^3 periodic, neighborhood 1: R = 0, and R = 1 with a z-slab of one eighth "
+                                   "refined; the six calls alternate in one run, every call synchronized (host clock), "
+                                   "median and min - max of the timed calls; kernel_ms: the same call between device "
+                                   "events; composed_curl: three gradient calls of two outputs each into six scratch "
+                                   "fields and three field_axpy calls, bitwise the fused curl's result"},
+            "bytes_per_cell": {"curl": "3 inputs 24 + face row 24 + 3 outputs 24 = 72 (+ 24 accumulating)",
+                               "divergence": "24 + 24 + 8 = 56", "field_axpy": "x 8 + y 8 read, y 8 written = 24",
+                               "composed_curl": "3 x (8 + 24 + 16) + 3 x 24 = 216"},
+            "uniform": uni, "refined": ref}
+    txt = json.dumps(line)
+    print(txt, flush=True)
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "particles_bench_curl.json")
     with open(out, "w") as f:
         f.write(txt + "\n")
 

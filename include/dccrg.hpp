@@ -1288,6 +1288,35 @@ public:
 		for (int d = 0; d < 3; d++) id[d] = out[size_t(d)] ? out[size_t(d)]->id() : -1;
 		detail::check(dccrgx_gradient(g_, in.id(), id, scale, region));
 	}
+	// out[k] = (accumulate: out[k] +) scale * the k-component of the curl of
+	// the three fields `in`, their derivatives gradient's bit for bit
+	// (nullptr: component not wanted); in's remote copies are read
+	void curl(const std::array<const Device_Field<double>*, 3>& in,
+	          const std::array<const Device_Field<double>*, 3>& out, const double scale = 1.0,
+	          const bool accumulate = false, const int region = DCCRGX_REGION_ALL) {
+		int fin[3], id[3];
+		for (int d = 0; d < 3; d++) {
+			if (!in[size_t(d)]) throw std::invalid_argument("a curl needs three input fields");
+			fin[d] = in[size_t(d)]->id();
+			id[d] = out[size_t(d)] ? out[size_t(d)]->id() : -1;
+		}
+		detail::check(dccrgx_curl(g_, fin, id, scale, accumulate ? 1 : 0, region));
+	}
+	// out = (accumulate: out +) scale * the divergence of the three fields `in`
+	void divergence(const std::array<const Device_Field<double>*, 3>& in, const Device_Field<double>& out,
+	                const double scale = 1.0, const bool accumulate = false, const int region = DCCRGX_REGION_ALL) {
+		int fin[3];
+		for (int d = 0; d < 3; d++) {
+			if (!in[size_t(d)]) throw std::invalid_argument("a divergence needs three input fields");
+			fin[d] = in[size_t(d)]->id();
+		}
+		detail::check(dccrgx_divergence(g_, fin, out.id(), scale, accumulate ? 1 : 0, region));
+	}
+	// y = y + (a * x) over the local cells, the product rounded before the sum
+	void field_axpy(const Device_Field<double>& y, const double a, const Device_Field<double>& x,
+	                const int region = DCCRGX_REGION_ALL) {
+		detail::check(dccrgx_field_axpy(g_, y.id(), a, x.id(), region));
+	}
 	// the records follow the mesh in every stop_refining: what user code does
 	// from refined_cell_data / unrefined_cell_data, on the device (a refined
 	// parent's records to the child at their position, the removed children's

@@ -589,6 +589,36 @@ int dccrgx_particles_boris(dccrgx_grid* g, int var_field, int record_doubles, in
  * one that is not 8 bytes wide, an output equal to the input or to another
  * output, all three outputs -1, a bad region. */
 int dccrgx_gradient(dccrgx_grid* g, int in_field, const int out_fields[3], double scale, int region);
+/* The curl and the divergence of the three fixed fp64 fields in_fields =
+ * (F_0, F_1, F_2) over the leaves, and y = y + a x on two such fields.  Let
+ * D_d(F)[c] be exactly the value `grad` of dccrgx_gradient's contract for the
+ * input F, the local leaf c and the dimension d, before the scaling: the same
+ * lengths, the same side rules (both sides, only +, only -, neither: 0), and
+ * the four values of a finer face summed as ((a0 + a1) + (a2 + a3)) / 4.0 in
+ * the face's stored order, which is the order dccrgx_gradient uses.  Every
+ * step below is one IEEE operation, in this order, so the results are bitwise
+ * what a caller combines from dccrgx_gradient's outputs with scale 1.0.
+ * curl:        r_0 = D_1(F_2) - D_2(F_1);  r_1 = D_2(F_0) - D_0(F_2);
+ *              r_2 = D_0(F_1) - D_1(F_0);  t_k = scale * r_k;
+ *              out_fields[k][c] = t_k, or with accumulate != 0
+ *              out_fields[k][c] + t_k.  out_fields[k] == -1: the component is
+ *              not wanted and not touched; at least one must be wanted.
+ * divergence:  r = (D_0(F_0) + D_1(F_1)) + D_2(F_2);  t = scale * r;
+ *              out_field[c] = t, or out_field[c] + t.
+ * field_axpy:  y[c] = y[c] + (a * x[c]): the product is rounded, then the sum.
+ * Every local cell of `region` is written (DCCRGX_REGION_*; inner then outer
+ * writes the bits of all, each only its own slots).  The remote copies of the
+ * inputs are read (update them first); remote-copy slots of an output or of y
+ * are never written.  The three inputs need not be distinct fields.  The
+ * Poisson solver's classification is not consulted.  DCCRGX_EINVAL, checked
+ * before the first write: a variable-size field, one that is not 8 bytes wide,
+ * an invalid field id, an output equal to an input or to another output, all
+ * three curl outputs -1, a bad region, x_field == y_field. */
+int dccrgx_curl(dccrgx_grid* g, const int in_fields[3], const int out_fields[3], double scale, int accumulate,
+                int region);
+int dccrgx_divergence(dccrgx_grid* g, const int in_fields[3], int out_field, double scale, int accumulate,
+                      int region);
+int dccrgx_field_axpy(dccrgx_grid* g, int y_field, double a, int x_field, int region);
 
 /* set_send_single_cells 6677 / get_send_single_cells 6684: one message per
  * cell (tag = position + 1) instead of one per process.  On, the remote
