@@ -143,7 +143,12 @@ _SIGS = {
     "dccrgx_curl": (C.c_int, [vp, P(C.c_int), P(C.c_int), C.c_double, C.c_int, C.c_int]),
     "dccrgx_divergence": (C.c_int, [vp, P(C.c_int), C.c_int, C.c_double, C.c_int, C.c_int]),
     "dccrgx_field_axpy": (C.c_int, [vp, C.c_int, C.c_double, C.c_int, C.c_int]),
-    "dccrgx_set_send_single_cells": (C.c_int, [vp, C.c_int]),
+    "dccrgx_field_reduce": (C.c_int, [vp, P(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_double)]),
+    "dccrgx_field_reduce_device": (C.c_int, [vp, P(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "dccrgx_particles_reduce": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, P(C.c_int), C.c_int, C.c_int,
+                                          P(C.c_double)]),
+    "dccrgx_particles_reduce_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, P(C.c_int), C.c_int, C.c_int, vp]),
+    "dccrgx_set_send_single_cells":(C.c_int, [vp, C.c_int]),
     "dccrgx_get_send_single_cells": (C.c_int, [vp, P(C.c_int)]),
     "dccrgx_set_field_window": (C.c_int, [vp, C.c_int, sz, sz]),
     "dccrgx_field_device_ptr": (C.c_int, [vp, C.c_int, P(vp)]),

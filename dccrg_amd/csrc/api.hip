@@ -13,6 +13,7 @@
 #include <unistd.h>
 
 #include "dccrgx_grid.hpp"
+#include "dccrgx_reduce.hpp"
 
 namespace dccrgx {
 
@@ -3545,6 +3546,98 @@ int dccrgx_field_axpy(dccrgx_grid* gp, int y_field, double a, int x_field, int r
 		k_field_axpy(reinterpret_cast<double*>(Y.data.p), a, reinterpret_cast<const double*>(field(g, x_field).data.p),
 		             s0, s1, g.s_comp);
 		k_time_end(g);
+		return 0;
+	});
+}
+
+namespace {
+// dccrgx_field_reduce into the device doubles d_out, everything queued on the
+// compute stream: the first stage over the region's slots (field_reduce_kernel,
+// poisson_kernels.hip), the fold of the blocks' partials, and with
+// `collective` the rank-ordered combine.  Every check precedes the first write.
+void field_reduce_device(Grid& g, const int* terms, int n, int by_volume, int region, int collective, double* d_out) {
+	DX_REQUIRE(g.initialized, "grid not initialized");
+	DX_REQUIRE(n >= 1 && n <= kRedTerms, "the number of terms must be 1 .. 16");
+	DX_REQUIRE(terms && d_out, "null pointer");
+	RedArgs T;
+	T.n = n;
+	int ids[2 * kRedTerms], cops[kRedTerms];
+	const double* fields[2 * kRedTerms];
+	auto staged = [&](int fid) {  // the column of a field's value
+		if (fid == -1) return kRedOne;
+		for (int i = 0; i < T.nv; i++)
+			if (ids[i] == fid) return i;
+		DX_REQUIRE(fixed_field(g, fid).elem == 8,
+		           "the fields of a reduction must be fixed-size fields of 8-byte elements (fp64)");
+		ids[T.nv] = fid;
+		fields[T.nv] = reinterpret_cast<const double*>(field(g, fid).data.p);
+		return T.nv++;
+	};
+	for (int j = 0; j < n; j++) {
+		const int op = terms[3 * j];
+		DX_REQUIRE(op >= DCCRGX_REDUCE_SUM && op <= DCCRGX_REDUCE_MAX_ABS, "unknown reduction (DCCRGX_REDUCE_*)");
+		T.op[j] = int8_t(op);
+		T.x0[j] = int8_t(staged(terms[3 * j + 1]));
+		T.x1[j] = int8_t(staged(terms[3 * j + 2]));
+		T.x2[j] = int8_t(by_volume && op == DCCRGX_REDUCE_SUM ? kRedExtra : kRedOne);
+		cops[j] = red_combine_op(op);
+	}
+	size_t s0, s1;
+	region_range(g, region, s0, s1);
+	if (collective && g.size > 1) comm_require(g, "a collective reduction");
+	const RedVolume V = reduce_volume(g, by_volume != 0);
+	hipStream_t s = g.s_comp;
+	const unsigned nb = s1 > s0 ? k_field_reduce_blocks(s1 - s0, T.nv) : 0;
+	k_time_begin(g);
+	if (nb) {
+		g.red_part.reserve(size_t(nb) * kRedTerms);
+		k_field_reduce(g.m, T, fields, V, s0, s1, nb, g.red_part.p, s);
+	}
+	k_reduce_fold(T, g.red_part.p, nb, d_out, s);
+	k_time_end(g);
+	if (collective) comm_allreduce_f64_ops_dev(g, d_out, d_out, n, cops, s);
+}
+}  // namespace
+
+int dccrgx_field_reduce_device(dccrgx_grid* gp, const int* terms, int n, int by_volume, int region, int collective,
+                               double* d_out) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		field_reduce_device(g, terms, n, by_volume, region, collective, d_out);
+		return 0;
+	});
+}
+
+// the device form into the grid's own doubles, then one synchronising copy
+int dccrgx_field_reduce(dccrgx_grid* gp, const int* terms, int n, int by_volume, int region, int collective,
+                        double* out) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		DX_REQUIRE(out, "null pointer");
+		g.red_val.reserve(kRedTerms);
+		field_reduce_device(g, terms, n, by_volume, region, collective, g.red_val.p);
+		d2h_small(out, g.red_val.p, size_t(n) * sizeof(double), g.s_comp);
+		return 0;
+	});
+}
+
+int dccrgx_particles_reduce_device(dccrgx_grid* gp, int var_field, int record_doubles, int weight_double,
+                                   const int* terms, int n, int collective, double* d_out) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		particles_reduce(g, var_field, record_doubles, weight_double, terms, n, collective, d_out);
+		return 0;
+	});
+}
+
+int dccrgx_particles_reduce(dccrgx_grid* gp, int var_field, int record_doubles, int weight_double, const int* terms,
+                            int n, int collective, double* out) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		DX_REQUIRE(out, "null pointer");
+		g.red_val.reserve(kRedTerms);
+		particles_reduce(g, var_field, record_doubles, weight_double, terms, n, collective, g.red_val.p);
+		d2h_small(out, g.red_val.p, size_t(n) * sizeof(double), g.s_comp);
 		return 0;
 	});
 }

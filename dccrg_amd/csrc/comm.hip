@@ -402,6 +402,56 @@ void comm_allreduce_f64_dev(Grid& g, const double* d_in, double* d_out, int coun
 	allreduce_through(g, g.red_all.p, d_in, d_out, count, op, s);
 }
 
+namespace {
+struct RankOps {
+	int8_t op[16];
+};
+
+// rank_combine_kernel with an operation per value
+__global__ void rank_combine_ops_kernel(const double* __restrict__ all, int P, int count, RankOps ops,
+                                        double* __restrict__ out) {
+#pragma clang fp contract(off)
+	const int k = int(blockIdx.x * blockDim.x + threadIdx.x);
+	if (k >= count) return;
+	int op = 0;
+#pragma unroll
+	for (int i = 0; i < 16; i++)
+		if (i == k) op = ops.op[i];
+	double acc = all[k];
+	for (int p = 1; p < P; p++) {
+		const double x = all[size_t(p) * size_t(count) + size_t(k)];
+		if (op == 0) acc += x;
+		else if (op == 1) acc = (x < acc) ? x : acc;
+		else acc = (acc < x) ? x : acc;
+	}
+	out[k] = acc;
+}
+}  // namespace
+
+// comm_allreduce_f64_dev with an operation per value (the terms of
+// dccrgx_field_reduce / dccrgx_particles_reduce): one all-gather, one combine
+void comm_allreduce_f64_ops_dev(Grid& g, const double* d_in, double* d_out, int count, const int* ops,
+                                hipStream_t s) {
+	if (count <= 0) return;
+	DX_REQUIRE(count <= 16 && ops, "allreduce: at most 16 values with an operation each");
+	const size_t bytes = size_t(count) * 8;
+	if (g.size == 1) {
+		if (d_in != d_out) HIP_CHECK(hipMemcpyAsync(d_out, d_in, bytes, hipMemcpyDeviceToDevice, s));
+		return;
+	}
+	comm_require(g, "allreduce");
+	DX_REQUIRE(s == g.s_comp, "device allreduce: the compute stream owns the gather buffer");
+	RankOps ro{};
+	for (int k = 0; k < count; k++) {
+		DX_REQUIRE(ops[k] >= 0 && ops[k] <= 2, "allreduce: op must be 0 (sum), 1 (min) or 2 (max)");
+		ro.op[k] = int8_t(ops[k]);
+	}
+	g.red_all.reserve(size_t(count) * size_t(g.size));
+	comm_allgather_dev(g, d_in, bytes, reinterpret_cast<uint8_t*>(g.red_all.p), s);
+	rank_combine_ops_kernel<<<1, 64, 0, s>>>(g.red_all.p, g.size, count, ro, d_out);
+	HIP_CHECK(hipGetLastError());
+}
+
 // MPI_Allreduce on host doubles (advection dt MIN, solve.hpp:317; sums): up,
 // gathered and combined on s_comm in a buffer of this call (value slot +
 // P x count gather), down

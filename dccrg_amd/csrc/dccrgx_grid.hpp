@@ -74,6 +74,15 @@ void particles_deposit_moments(Grid& g, int fid, int K, int shape, int weight_do
 // the Boris kick of dccrgx.h with E at e_first .., B at b_first ..,
 // h = factor q, for every record of a local cell
 void particles_boris(Grid& g, int fid, int K, int e_first, int b_first, int weight_double, double factor);
+// n reductions terms[3 j] (DCCRGX_REDUCE_*) over (q * record[terms[3 j + 1]]) *
+// record[terms[3 j + 2]] (-1: 1.0) of the local cells' records into the device
+// doubles d_out, queued on the compute stream; collective: combined over the
+// processes in rank order
+void particles_reduce(Grid& g, int fid, int K, int weight_double, const int* terms, int n, int collective,
+                      double* d_out);
+// the source of V_c for dccrgx_field_reduce's by_volume (the deposit's
+// per_volume rule and cell_volume's bits)
+RedVolume reduce_volume(Grid& g, bool by_volume);
 // the active stretched geometry's coordinates on the device (x, then y, then
 // z, packed), uploaded at first use
 const double* stretched_device(Grid& g);

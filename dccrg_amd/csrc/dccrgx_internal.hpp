@@ -639,6 +639,9 @@ struct Grid {
 	RangeLevel rmap_spare_rl[kRangeLevels] = {};
 	int rmap_spare_rlev = 0;
 	DBuf<double> red_all;  // P x count all-gathered values of comm_allreduce_f64_dev (s_comp only)
+	// dccrgx_field_reduce / dccrgx_particles_reduce (s_comp only): the blocks'
+	// partials, kRedTerms per block, and the host form's results on the device
+	DBuf<double> red_part, red_val;
 	// pinned host staging of the host-exchange transport (comm.hip
 	// move_bytes), grow-only, freed with the grid: the device <-> host legs
 	// then run on the copy engines instead of the runtime's pageable path
@@ -827,6 +830,9 @@ std::vector<std::vector<uint64_t>> comm_alltoall_u64(Grid& g, const std::vector<
 void comm_allreduce_f64(Grid& g, double* v, int count, int op);  // 0 sum, 1 min, 2 max
 // the same on device values, queued on s (stream-ordered over RCCL)
 void comm_allreduce_f64_dev(Grid& g, const double* d_in, double* d_out, int count, int op, hipStream_t s);
+// the same with an operation per value (ops[k]: 0 sum, 1 min, 2 max), count <= 16
+void comm_allreduce_f64_ops_dev(Grid& g, const double* d_in, double* d_out, int count, const int* ops,
+                                hipStream_t s);
 uint64_t comm_allreduce_max_u64(Grid& g, uint64_t v);
 // device payloads: per peer one message of known size each way.  cell > 0:
 // the message is a run of cells of `cell` bytes each way, which
@@ -1239,6 +1245,72 @@ void k_divergence(const MapCtx& m, const double l0[3], const StretchedView& G, c
                   hipStream_t s);
 // dccrgx_field_axpy: y = y + (a * x) over the slots [s0, s1)
 void k_field_axpy(double* y, double a, const double* x, size_t s0, size_t s1, hipStream_t s);
+
+// --- reductions (dccrgx_reduce.hpp) ---------------------------------------
+constexpr int kRedTerms = 16;   // terms of one call
+constexpr int kRedValues = 33;  // distinct values of an element: two per term and the records' weight
+// the terms of a reduction, a kernel argument: operation j (DCCRGX_REDUCE_*)
+// over (x0 * x1) * x2, each factor an index into the element's staged values,
+// or kRedOne (1.0), or kRedExtra (the element's extra value)
+struct RedArgs {
+	int n = 0, nv = 0;  // terms, staged values per element
+	int8_t op[kRedTerms] = {}, x0[kRedTerms] = {}, x1[kRedTerms] = {}, x2[kRedTerms] = {};
+};
+// the geometry a cell's volume (lx ly) lz is formed from (particles.hip:
+// make_wgeo, cell_volume)
+struct WGeo {
+	double start[3], l0[3], period[3];  // period: double(length) * l0
+	double inv_fine;                    // 1 / 2^R
+	int per[3];
+	const double* c;  // stretched: the packed coordinates (lengths only), else nullptr
+	uint32_t off[3];
+};
+// (lx * ly) * lz with geometry_fill_kernel's lengths, Cartesian or stretched
+__device__ __forceinline__ double cell_volume(const MapCtx& m, const WGeo& G, uint64_t id) {
+#pragma clang fp contract(off)
+	uint64_t ind[3] = {0, 0, 0};
+	const int lvl = map_indices(m, id, ind[0], ind[1], ind[2]);
+	const double div = double(uint64_t(1) << (lvl < 0 ? 0 : lvl));
+	double L[3];
+#pragma unroll
+	for (int d = 0; d < 3; d++) {
+		if (G.c) {
+			const uint64_t i0 = ind[d] >> m.R;
+			const double c0 = G.c[G.off[d] + i0];
+			const double extent = G.c[G.off[d] + i0 + 1] - c0;
+			L[d] = extent / div;
+		} else {
+			const double sf = 1.0 / div;
+			L[d] = G.l0[d] * sf;
+		}
+	}
+	const double a = L[0] * L[1];
+	return a * L[2];
+}
+// where dccrgx_field_reduce takes V_c from: nothing (mode 0), the level's
+// volume of a Cartesian geometry (1: vol0 * 2^(-3 level), the level from the
+// low five bits of slot_lvl[c], with vol0 the
+// level-0 volume formed as cell_volume forms it; the scaling by a power of
+// two is exact, so these are cell_volume's bits for every length that is not
+// subnormal; slot_lvl == nullptr: every cell at level 0), or cell_volume of
+// the cell's id (2: stretched)
+struct RedVolume {
+	int mode = 0;
+	double vol0 = 1.0;
+	const uint8_t* slot_lvl = nullptr;
+	const uint64_t* slot_ids = nullptr;
+	WGeo G = {};
+};
+// blocks of the first stage over n elements (a function of n and the values
+// per element only), and the partials it needs
+unsigned k_field_reduce_blocks(size_t n, int nv);
+// first stage of dccrgx_field_reduce over the slots [s0, s1): part[b *
+// kRedTerms + j] = block b's partial of term j; fields[f] is staged value f
+void k_field_reduce(const MapCtx& m, const RedArgs& T, const double* const* fields, const RedVolume& V, size_t s0,
+                    size_t s1, unsigned nb, double* part, hipStream_t s);
+// second stage of both reductions: out[j] = the nb partials of term j folded
+// in a fixed order (nb == 0: the operation's identity)
+void k_reduce_fold(const RedArgs& T, const double* part, unsigned nb, double* out, hipStream_t s);
 
 }  // namespace dccrgx
 

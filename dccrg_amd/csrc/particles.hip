@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "dccrgx_grid.hpp"
+#include "dccrgx_reduce.hpp"
 
 // x + v dt, x +- L ceil(d / L) and (x - start) / l are separately rounded
 // operations in the reference; hipcc fuses a * b + c by default
@@ -1174,14 +1175,6 @@ void particles_follow_rebuild(Grid& g, Field& f, const uint64_t* old_ids, size_t
 //             up to four fields per pass, stored into the record.
 namespace {
 
-struct WGeo {
-	double start[3], l0[3], period[3];  // period: double(length) * l0
-	double inv_fine;                    // 1 / 2^R
-	int per[3];
-	const double* c;  // stretched: the packed coordinates (lengths only), else nullptr
-	uint32_t off[3];
-};
-
 struct CellBox {
 	double lo[3], L[3], hi[3];
 };
@@ -1205,27 +1198,8 @@ __device__ __forceinline__ void cell_box(const MapCtx& m, const WGeo& G, uint64_
 	}
 }
 
-// (lx * ly) * lz with geometry_fill_kernel's lengths, Cartesian or stretched
-__device__ __forceinline__ double cell_volume(const MapCtx& m, const WGeo& G, uint64_t id) {
-	uint64_t ind[3] = {0, 0, 0};
-	const int lvl = map_indices(m, id, ind[0], ind[1], ind[2]);
-	const double div = double(uint64_t(1) << (lvl < 0 ? 0 : lvl));
-	double L[3];
-#pragma unroll
-	for (int d = 0; d < 3; d++) {
-		if (G.c) {
-			const uint64_t i0 = ind[d] >> m.R;
-			const double c0 = G.c[G.off[d] + i0];
-			const double extent = G.c[G.off[d] + i0 + 1] - c0;
-			L[d] = extent / div;
-		} else {
-			const double sf = 1.0 / div;
-			L[d] = G.l0[d] * sf;
-		}
-	}
-	const double a = L[0] * L[1];
-	return a * L[2];
-}
+// (cell_volume, (lx * ly) * lz with geometry_fill_kernel's lengths, stands in
+// dccrgx_internal.hpp beside WGeo: dccrgx_field_reduce's by_volume uses it too)
 
 __device__ __forceinline__ double overlap_1d(double a, double b, double lo, double hi) {
 	const double top = fmin(b, hi);
@@ -1630,6 +1604,41 @@ __global__ __launch_bounds__(kPB) void particles_boris_kernel(double* __restrict
 	}
 }
 
+// dccrgx_particles_reduce, first stage: a thread per record of the first N of
+// the pool (the local cells'), as particles_accelerate_kernel walks them.
+// Only the doubles the terms name are read (D.d, each once per record, eight
+// loads in flight), staged in the thread's LDS column; 128 threads, so that
+// 33 values a record fit 64 KB.  Block b's partials go to part[b * kRedTerms ..].
+constexpr int kRP = 128;
+
+struct RedDoubles {
+	int d[kRedValues];
+};
+
+__global__ __launch_bounds__(kRP) void particles_reduce_kernel(const double* __restrict__ pool, size_t N, int K,
+                                                               const RedArgs T, const RedDoubles D,
+                                                               double* __restrict__ part) {
+	extern __shared__ double red_sh[];
+	double acc[kRedTerms];
+	red_init(T, acc);
+	const int col = int(threadIdx.x);
+	for (size_t p = blockIdx.x * size_t(kRP) + threadIdx.x; p < N; p += size_t(gridDim.x) * kRP) {
+		const double* r = pool + p * size_t(K);
+		for (int f0 = 0; f0 < T.nv; f0 += 8) {
+			double v[8];
+#pragma unroll
+			for (int k = 0; k < 8; k++)
+				if (f0 + k < T.nv) v[k] = r[D.d[f0 + k]];
+#pragma unroll
+			for (int k = 0; k < 8; k++)
+				if (f0 + k < T.nv) red_sh[(f0 + k) * kRP + col] = v[k];
+		}
+		red_accumulate(T, red_sh, kRP, col, 1.0, acc);
+	}
+	const double r = red_block<kRP>(T, red_sh, acc);
+	if (int(threadIdx.x) < T.n) part[size_t(blockIdx.x) * kRedTerms + threadIdx.x] = r;
+}
+
 Field& fp64_cell_field(Grid& g, int fid, const char* what) {
 	Field& F = fixed_field(g, fid);
 	DX_REQUIRE(F.elem == 8, std::string(what) + " must be a fixed-size field of 8-byte elements (fp64)");
@@ -1865,6 +1874,88 @@ void particles_boris(Grid& g, int fid, int K, int e_first, int b_first, int weig
 	HIP_CHECK(hipGetLastError());
 	field_written(f);
 	HIP_CHECK(hipStreamSynchronize(s));  // ofirst goes out of scope
+}
+
+// up to 16 reductions over the records of the local cells, the results in
+// device memory d_out, queued on the compute stream.  The checks of the
+// cells' byte counts and the number of local records (which sizes the grid)
+// are read back first, as in every particle call; from there on nothing
+// waits on the host.
+void particles_reduce(Grid& g, int fid, int K, int weight_double, const int* terms, int n, int collective,
+                      double* d_out) {
+	Field& f = field(g, fid);
+	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	DX_REQUIRE(n >= 1 && n <= kRedTerms, "the number of terms must be 1 .. 16");
+	DX_REQUIRE(terms && d_out, "null pointer");
+	DX_REQUIRE(K >= 3, "a particle record has at least 3 doubles (the position)");
+	DX_REQUIRE(weight_double == -1 || (weight_double >= 3 && weight_double < K),
+	           "weight_double must be -1 (q = 1) or a double of the record past the position (3 <= weight_double < "
+	           "record_doubles)");
+	RedArgs T;
+	RedDoubles D{};
+	T.n = n;
+	auto staged = [&](int d) {  // the column of the record's double d
+		if (d == -1) return kRedOne;
+		for (int i = 0; i < T.nv; i++)
+			if (D.d[i] == d) return i;
+		D.d[T.nv] = d;
+		return T.nv++;
+	};
+	int cops[kRedTerms];
+	for (int j = 0; j < n; j++) {
+		const int op = terms[3 * j], u = terms[3 * j + 1], v = terms[3 * j + 2];
+		DX_REQUIRE(op >= DCCRGX_REDUCE_SUM && op <= DCCRGX_REDUCE_MAX_ABS, "unknown reduction (DCCRGX_REDUCE_*)");
+		DX_REQUIRE((u == -1 || (u >= 3 && u < K)) && (v == -1 || (v >= 3 && v < K)),
+		           "a term's factor must be -1 (1.0) or a double of the record past the position (3 <= factor < "
+		           "record_doubles)");
+		T.op[j] = int8_t(op);
+		T.x0[j] = int8_t(staged(weight_double));
+		T.x1[j] = int8_t(staged(u));
+		T.x2[j] = int8_t(staged(v));
+		cops[j] = red_combine_op(op);
+	}
+	if (collective && g.size > 1) comm_require(g, "a collective reduction");
+	DBuf<uint32_t> ofirst;
+	const size_t N_all = particle_mesh_prepare(g, f, K, 0, false, ofirst);
+	const size_t nl = g.n_local;
+	hipStream_t s = g.s_comp;
+	size_t N = 0;
+	if (N_all && nl) N = size_t(var_total(f, nl, s) / (uint64_t(K) * sizeof(double)));  // the local cells' records
+	const unsigned nb = N ? grid_for(N, kRP, 4096) : 0;
+	k_time_begin(g);
+	if (nb) {
+		g.red_part.reserve(size_t(nb) * kRedTerms);
+		const size_t lds = std::max(size_t(T.nv) * kRP, size_t(kRedTerms) * (kRP / 64)) * sizeof(double);
+		particles_reduce_kernel<<<nb, kRP, lds, s>>>(reinterpret_cast<const double*>(f.data.p), N, K, T, D,
+		                                             g.red_part.p);
+		HIP_CHECK(hipGetLastError());
+	}
+	k_reduce_fold(T, g.red_part.p, nb, d_out, s);
+	k_time_end(g);
+	if (collective) comm_allreduce_f64_ops_dev(g, d_out, d_out, n, cops, s);
+}
+
+// where dccrgx_field_reduce's by_volume takes V_c from: cell_volume, as the
+// deposit's per_volume (and its rule for a stretched block without
+// coordinates); on a Cartesian geometry the level's volume, the same bits
+RedVolume reduce_volume(Grid& g, bool by_volume) {
+	RedVolume V;
+	if (!by_volume) return V;
+	require_geometry(g);
+	V.G = make_wgeo(g, true);
+	V.slot_ids = g.slot_ids.p;
+	if (g.str.active) {
+		V.mode = 2;
+		return V;
+	}
+	V.mode = 1;
+	const double a = g.l0[0] * g.l0[1];
+	V.vol0 = a * g.l0[2];
+	if (g.R > 0) {
+		ensure_face(g);  // the level byte of every slot
+		V.slot_lvl = g.slot_lvl.p;
+	}
+	return V;
 }
 
 }  // namespace dccrgx

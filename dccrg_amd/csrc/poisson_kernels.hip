@@ -10,9 +10,11 @@
 // Per-cell arithmetic follows the reference expression by expression with
 // contraction off, so per-cell results equal the reference's for the same
 // inputs; only the global sums differ in summation order.
+#include <algorithm>
 #include <cfloat>
 
 #include "dccrgx_internal.hpp"
+#include "dccrgx_reduce.hpp"
 
 namespace dccrgx {
 
@@ -786,7 +788,134 @@ __global__ __launch_bounds__(BS) void field_axpy_kernel(double* __restrict__ y, 
 	}
 }
 
+// dccrgx_field_reduce, first stage: one streaming pass over the slots
+// [s0, s1) for all terms.  A thread takes W cells a pass and stages every
+// distinct field's value of them in its LDS columns (dccrgx_reduce.hpp), each
+// field loaded once per cell, eight loads in flight.  W == 2: pairs from the
+// first even slot on as 16-byte loads (a field's array starts 256-byte
+// aligned), a leading odd slot by the first thread and a trailing single one
+// on their own, as field_axpy_kernel has them; 2 KB of LDS per field and
+// cell of the pair, so up to 16 fields.  W == 1 takes the 17 to 32 fields
+// that 16 terms can name.
+constexpr int kRB = 256;
+constexpr int kRedFields = 32;
+
+struct RedFields {
+	const double* f[kRedFields];
+};
+
+// V_c of slot c (RedVolume)
+__device__ __forceinline__ double red_cell_volume(const MapCtx& m, const RedVolume& V, size_t c) {
+#pragma clang fp contract(off)
+	if (V.mode == 2) return cell_volume(m, V.G, V.slot_ids[c]);
+	if (V.mode != 1) return 1.0;
+	if (!V.slot_lvl) return V.vol0;
+	const int lvl = V.slot_lvl[c] & 31;  // (the byte's upper bits hold the octant)
+	const double sf3 = __longlong_as_double((1023ll - 3ll * lvl) << 52);  // 2^(-3 level)
+	return V.vol0 * sf3;
+}
+
+template <int W>
+__global__ __launch_bounds__(kRB) void field_reduce_kernel(const MapCtx m, const RedArgs T, const RedFields F,
+                                                           const RedVolume V, size_t s0, size_t s1,
+                                                           double* __restrict__ part) {
+#pragma clang fp contract(off)
+	extern __shared__ double red_sh[];
+	constexpr int STRIDE = kRB * W;
+	double acc[kRedTerms];
+	red_init(T, acc);
+	const int col = int(threadIdx.x);
+	auto single = [&](size_t c) {
+		for (int f0 = 0; f0 < T.nv; f0 += 8) {
+			double v[8];
+#pragma unroll
+			for (int k = 0; k < 8; k++)
+				if (f0 + k < T.nv) v[k] = F.f[f0 + k][c];
+#pragma unroll
+			for (int k = 0; k < 8; k++)
+				if (f0 + k < T.nv) red_sh[(f0 + k) * STRIDE + col] = v[k];
+		}
+		red_accumulate(T, red_sh, STRIDE, col, red_cell_volume(m, V, c), acc);
+	};
+	if constexpr (W == 1) {
+		for (size_t c = s0 + blockIdx.x * size_t(kRB) + threadIdx.x; c < s1; c += size_t(gridDim.x) * kRB) single(c);
+	} else {
+		const size_t b = (s0 + 1) & ~size_t(1);
+		if (b != s0 && blockIdx.x == 0 && threadIdx.x == 0) single(s0);  // (s0 < s1: no launch for an empty range)
+		for (size_t i = b + 2 * (blockIdx.x * size_t(kRB) + threadIdx.x); i < s1; i += 2 * size_t(gridDim.x) * kRB) {
+			if (i + 1 < s1) {
+				for (int f0 = 0; f0 < T.nv; f0 += 8) {
+					double2 v[8];
+#pragma unroll
+					for (int k = 0; k < 8; k++)
+						if (f0 + k < T.nv) v[k] = *reinterpret_cast<const double2*>(F.f[f0 + k] + i);
+#pragma unroll
+					for (int k = 0; k < 8; k++)
+						if (f0 + k < T.nv) {
+							red_sh[(f0 + k) * STRIDE + col] = v[k].x;
+							red_sh[(f0 + k) * STRIDE + kRB + col] = v[k].y;
+						}
+				}
+				red_accumulate(T, red_sh, STRIDE, col, red_cell_volume(m, V, i), acc);
+				red_accumulate(T, red_sh, STRIDE, kRB + col, red_cell_volume(m, V, i + 1), acc);
+			} else {
+				single(i);
+			}
+		}
+	}
+	const double r = red_block<kRB>(T, red_sh, acc);
+	if (int(threadIdx.x) < T.n) part[size_t(blockIdx.x) * kRedTerms + threadIdx.x] = r;
+}
+
+// second stage of dccrgx_field_reduce and dccrgx_particles_reduce: block j
+// folds the nb partials of term j, thread t the partials t, t + kRB, .. in
+// that order, then the block as in the first stage; nb == 0 leaves the
+// operation's identity
+__global__ __launch_bounds__(kRB) void reduce_fold_kernel(const RedArgs T, const double* __restrict__ part, unsigned nb,
+                                                          double* __restrict__ out) {
+#pragma clang fp contract(off)
+	__shared__ double sh[kRB / 64];
+	const int j = int(blockIdx.x);
+	const int cop = red_combine_op(T.op[j]);
+	double v = red_identity(T.op[j]);
+	for (unsigned i = threadIdx.x; i < nb; i += kRB) v = red_combine(cop, v, part[size_t(i) * kRedTerms + j]);
+	for (int o = 32; o > 0; o >>= 1) v = red_combine(cop, v, __shfl_down(v, o, 64));
+	if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		double r = sh[0];
+		for (int i = 1; i < kRB / 64; i++) r = red_combine(cop, r, sh[i]);
+		out[j] = r;
+	}
+}
+
 }  // namespace
+
+unsigned k_field_reduce_blocks(size_t n, int nv) {
+	if (!n) return 0;
+	const size_t per = size_t(kRB) * (nv <= kRedFields / 2 ? 2 : 1);
+	return grid_for(n + 1, unsigned(per), 2048);  // (+ 1: the pairs start at the first even slot)
+}
+
+void k_field_reduce(const MapCtx& m, const RedArgs& T, const double* const* fields, const RedVolume& V, size_t s0,
+                    size_t s1, unsigned nb, double* part, hipStream_t s) {
+	if (s1 <= s0 || !nb) return;
+	DX_REQUIRE(T.nv <= kRedFields, "more distinct fields than a reduction stages");
+	RedFields F{};
+	for (int f = 0; f < T.nv; f++) F.f[f] = fields[f];
+	const int W = T.nv <= kRedFields / 2 ? 2 : 1;
+	const size_t lds = std::max(size_t(T.nv) * kRB * W, size_t(kRedTerms) * (kRB / 64)) * sizeof(double);
+	if (W == 2)
+		field_reduce_kernel<2><<<nb, kRB, lds, s>>>(m, T, F, V, s0, s1, part);
+	else
+		field_reduce_kernel<1><<<nb, kRB, lds, s>>>(m, T, F, V, s0, s1, part);
+	HIP_CHECK(hipGetLastError());
+}
+
+void k_reduce_fold(const RedArgs& T, const double* part, unsigned nb, double* out, hipStream_t s) {
+	reduce_fold_kernel<<<unsigned(T.n), kRB, 0, s>>>(T, part, nb, out);
+	HIP_CHECK(hipGetLastError());
+}
 
 void k_gradient(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
                 const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine, const double* in,

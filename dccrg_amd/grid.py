@@ -15,6 +15,7 @@ import numpy as np
 from ._lib import EINVAL, ENOTFOUND, ERANGE, EXCHANGE_FN, DccrgError, check, lib
 
 REGION = {"all": 0, "inner": 1, "outer": 2}
+REDUCE = {"sum": 0, "min": 1, "max": 2, "max_abs": 3}  # DCCRGX_REDUCE_*
 DEFAULT_HOOD = -0xDCC  # default_neighborhood_id (dccrg.hpp:93)
 CELLS = {"local": 0, "inner": 1, "outer": 2, "remote": 3, "all": 4}
 CSR_KIND = {"of": 0, "to": 1, "face": 2, "iterator": 3}
@@ -1043,6 +1044,72 @@ class Dccrg:
         """y = y + (a * x) in every local cell of `region`, the product rounded
         before the sum; two distinct float64 Fields."""
         check(lib().dccrgx_field_axpy(self.h, y.id, float(a), x.id, REGION[region]))
+
+    def _reduce_out(self, n, out):
+        if out is None or isinstance(out, int):
+            return out
+        if out.numel() < n:
+            raise ValueError("out holds fewer elements than there are terms")
+        return out
+
+    def field_reduce(self, terms, by_volume=False, region="all", collective=False, out=None):
+        """Up to 16 reductions over the local cells of `region` in one pass on
+        the device.  `terms` is a list of (op, a, b): op "sum", "min", "max"
+        or "max_abs" over a[c] * b[c], a and b float64 Fields or None for 1.0
+        (a is b: a square).  by_volume multiplies the terms of a sum by the
+        cell's volume (lx ly) lz.  collective combines the processes' values
+        in rank order (every process calls).  Returns a NumPy array of
+        len(terms) doubles; with out= a float64 torch tensor on the GPU (or a
+        device address) its first len(terms) elements are filled on the
+        compute stream, nothing waits for them, and `out` is returned.  Sums
+        have a fixed order (two calls give the same bits), extrema are exact;
+        over no cells: 0, +inf, -inf, 0.  include/dccrgx.h has the contract."""
+        terms = [tuple(t) for t in terms]
+        if any(len(t) != 3 for t in terms):
+            raise ValueError("a term is (op, a, b)")
+        flat = []
+        for op, a, b in terms:
+            flat += [REDUCE[op] if isinstance(op, str) else int(op), -1 if a is None else a.id,
+                     -1 if b is None else b.id]
+        n = len(terms)
+        arr = (C.c_int * max(len(flat), 1))(*flat)
+        if out is not None:
+            out = self._reduce_out(n, out)
+            check(lib().dccrgx_field_reduce_device(self.h, arr, n, int(bool(by_volume)), REGION[region],
+                                                   int(bool(collective)), _dev_ptr(out)))
+            return out
+        res = np.empty(max(n, 1), np.float64)
+        check(lib().dccrgx_field_reduce(self.h, arr, n, int(bool(by_volume)), REGION[region], int(bool(collective)),
+                                        res.ctypes.data_as(C.POINTER(C.c_double))))
+        return res[:n]
+
+    def particles_reduce(self, field, terms, record_doubles, weight=-1, collective=False, out=None):
+        """Up to 16 reductions over the records of the local cells in one walk
+        on the device.  `terms` is a list of (op, u, v) over (q u) v with u, v
+        doubles of the record (None or -1: 1.0) and q the double `weight`
+        (None or -1: 1): weight -1 and ("sum", None, None) counts the records,
+        ("sum", None, None) is the total charge, ("sum", 3, None) the
+        x-momentum, ("max_abs", 3, None) with weight -1 max |v_x|.  collective,
+        out and the results as for field_reduce."""
+        terms = [tuple(t) for t in terms]
+        if any(len(t) != 3 for t in terms):
+            raise ValueError("a term is (op, u, v)")
+        flat = []
+        for op, u, v in terms:
+            flat += [REDUCE[op] if isinstance(op, str) else int(op), -1 if u is None else int(u),
+                     -1 if v is None else int(v)]
+        n = len(terms)
+        arr = (C.c_int * max(len(flat), 1))(*flat)
+        w = -1 if weight is None else int(weight)
+        if out is not None:
+            out = self._reduce_out(n, out)
+            check(lib().dccrgx_particles_reduce_device(self.h, field.id, int(record_doubles), w, arr, n,
+                                                       int(bool(collective)), _dev_ptr(out)))
+            return out
+        res = np.empty(max(n, 1), np.float64)
+        check(lib().dccrgx_particles_reduce(self.h, field.id, int(record_doubles), w, arr, n, int(bool(collective)),
+                                            res.ctypes.data_as(C.POINTER(C.c_double))))
+        return res[:n]
 
     # ---- built-in sweeps ------------------------------------------------------------
     def gol_step(self, state: Field, region="all"):

@@ -38,7 +38,15 @@ calls alternate, each synchronized; median and min - max of the timed ones.
 --curl measures Dccrg.curl (plain and accumulating), Dccrg.divergence,
 Dccrg.gradient and Dccrg.field_axpy beside the curl a caller composed before
 them from three gradient calls into six scratch fields and three axpys, the
-six alternating in one run on --pic's two gradient grids."""
+six alternating in one run on --pic's two gradient grids.
+
+--reduce measures Dccrg.field_reduce on the same two grids: the seven-term
+energy call (six squares by volume and max |div B|) against the same values
+from seven single-term calls, Dccrg.field_axpy as the streaming yardstick and
+the host way (download of the seven fields and NumPy), alternating in one run,
+between device events and on the host clock; and Dccrg.particles_reduce of
+count, charge, momenta and squares beside particles_accelerate on the K = 10
+pool."""
 from __future__ import annotations
 
 import argparse
@@ -177,6 +185,10 @@ def main(argv=None):
                    help="dccrgx_curl (plain and accumulating), dccrgx_divergence, dccrgx_gradient, dccrgx_field_axpy and "
                         "the curl composed from three gradients and three axpys, alternating in one run on the uniform "
                         "and on --adapt's refined grid; writes profiles/particles_bench_curl.json unless --out")
+    p.add_argument("--reduce", action="store_true",
+                   help="measure Dccrg.field_reduce (seven terms in one call against seven calls, field_axpy and the "
+                        "host way) on the uniform and on --adapt's refined grid, and Dccrg.particles_reduce beside "
+                        "particles_accelerate; writes profiles/particles_bench_reduce.json unless --out")
     p.add_argument("--pic-iterations", type=int, default=10, help="with --pic: BiCG iterations of a solve (min = max)")
     p.add_argument("--repeats", type=int, default=3)
     p.add_argument("--parent", default=None,
@@ -187,6 +199,8 @@ def main(argv=None):
 
     import torch  # noqa: F401  (one HIP runtime for the process)
 
+    if a.reduce:
+        return main_reduce(a)
     if a.curl:
         return main_curl(a)
     if a.pic:
@@ -863,6 +877,156 @@ def main_curl(a):
     print(txt, flush=True)
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                 "particles_bench_curl.json")
+    with open(out, "w") as f:
+        f.write(txt + "\n")
+
+
+# field_reduce_kernel per local cell: the seven fields of the energy call, 56 B (+ the level byte on a refined grid,
+# where the volume follows the level); the particle reduce names 4 of a record's 10 doubles (32 B of its 80 B)
+REDUCE_FIELD_BYTES = 56
+
+
+def _event_and_host_ms(g, calls, warmup, steps):
+    """warmup + steps rounds over `calls` in turn; per name the time between
+    device events (dccrgx_kernel_timing, summed over the call's launches; None
+    for a call that times nothing) and the synchronized host clock."""
+    ev, host = {k: [] for k in calls}, {k: [] for k in calls}
+    for i in range(warmup + max(steps, 1)):
+        for name, call in calls.items():
+            g.synchronize()
+            g.kernel_timing(1)
+            t0 = time.perf_counter()
+            call()
+            g.synchronize()
+            dt = (time.perf_counter() - t0) * 1e3
+            kms, kn = g.kernel_timing(0)
+            if i >= warmup:
+                host[name].append(dt)
+                if kn:
+                    ev[name].append(kms)
+    res = {}
+    for k in calls:
+        res[k] = dict(host_ms=float(np.median(host[k])), host_min_ms=float(min(host[k])), host_max_ms=float(max(host[k])))
+        if ev[k]:
+            res[k].update(ms=float(np.median(ev[k])), min_ms=float(min(ev[k])), max_ms=float(max(ev[k])), runs_ms=ev[k])
+    return res
+
+
+def measure_reduce_fields(a, refined):
+    """The seven-term energy call (six squares by volume and max |div B|)
+    against the same values from seven single-term calls, field_axpy and the
+    host way (download of the seven fields and NumPy), interleaved in one run."""
+    import torch
+
+    import dccrg_amd
+
+    n = a.base
+    g = dccrg_amd.Dccrg(0, 1, 0).set_initial_length((n, n, n)).set_neighborhood_length(1)
+    g.set_maximum_refinement_level(1 if refined else 0).set_periodic(True, True, True).initialize()
+    if refined:
+        _refine_slab(g, n)
+    g.set_geometry((0, 0, 0), (1, 1, 1))
+    nc = int(g.n_local)
+    rng = np.random.default_rng(2)
+    F = [g.add_field(nm, np.float64, False) for nm in ("Ex", "Ey", "Ez", "Bx", "By", "Bz", "div")]
+    for f in F:
+        f.set(rng.random(g.n_slots) * 2 - 1)
+    y = g.add_field("y", np.float64, False)
+    y.set(np.zeros(g.n_slots))
+    terms = [("sum", f, f) for f in F[:6]] + [("max_abs", F[6], None)]
+    one, seven = torch.zeros(7, dtype=torch.float64, device="cuda"), torch.zeros(7, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    host = {}
+
+    def host_way():
+        v = [f.get(0, nc) for f in F]
+        host["values"] = [float(np.dot(x, x)) for x in v[:6]] + [float(np.max(np.abs(v[6])))]
+
+    calls = {"reduce_7_terms": lambda: g.field_reduce(terms, True, out=one),
+             "reduce_7_calls": lambda: [g.field_reduce([t], True, out=seven[j:j + 1]) for j, t in enumerate(terms)],
+             "field_axpy": lambda: g.field_axpy(y, 1e-3, F[0]),
+             "host_way": host_way}
+    res = _event_and_host_ms(g, calls, a.warmup, a.steps)
+    g.synchronize()
+    got, single = one.cpu().numpy(), seven.cpu().numpy()
+    # one call and seven calls give the same bits (the order depends on the number of cells only)
+    assert np.array_equal(got.view(np.uint64), single.view(np.uint64)), (got, single)
+    assert got[6] == host["values"][6]
+    if not refined:  # (V = 1: the host's sums are the same sums)
+        assert np.allclose(got[:6], host["values"][:6], rtol=1e-12, atol=0), (got, host["values"])
+    g.close()
+    b = REDUCE_FIELD_BYTES + (1 if refined else 0)
+
+    def roofline(t, bytes_per_cell):
+        ach = nc * bytes_per_cell / (t / 1e3) / 1e9
+        return {"bound": "hbm", "bytes_per_cell": bytes_per_cell, "achieved": ach, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                "frac": ach / PEAK_HBM_GBS}
+
+    for name, bb in (("reduce_7_terms", b), ("reduce_7_calls", b + (5 if refined else 0)), ("field_axpy", AXPY_BYTES)):
+        res[name]["roofline"] = roofline(res[name]["ms"], bb)
+    res["cells"] = nc
+    res["host_way"]["bytes_moved"] = 7 * 8 * nc
+    res["one_call_over_seven_calls"] = res["reduce_7_terms"]["ms"] / res["reduce_7_calls"]["ms"]
+    res["one_call_over_seven_calls_host_clock"] = res["reduce_7_terms"]["host_ms"] / res["reduce_7_calls"]["host_ms"]
+    res["one_call_over_host_way"] = res["reduce_7_terms"]["host_ms"] / res["host_way"]["host_ms"]
+    res["frac_of_peak_over_field_axpy"] = (res["reduce_7_terms"]["roofline"]["frac"] /
+                                           res["field_axpy"]["roofline"]["frac"])
+    return res
+
+
+def measure_reduce_particles(a):
+    """Count, charge, three momenta and three squares of every record in one
+    call beside particles_accelerate, which walks the same pool."""
+    import torch
+
+    Kb, E0 = 10, 7
+    g, fld, nc, sums = _moments_pool(a, Kb)
+    terms = [("sum", None, None), ("sum", PIC_Q, None), ("sum", 3, None), ("sum", 4, None), ("sum", 5, None),
+             ("sum", 3, 3), ("sum", 4, 4), ("sum", 5, 5)]
+    out = torch.zeros(8, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    calls = {"particles_reduce": lambda: g.particles_reduce(fld, terms, Kb, -1, out=out),
+             "accelerate": lambda: g.particles_accelerate(fld, E0, Kb, 1e-3, PIC_Q)}
+    res = _event_and_host_ms(g, calls, a.warmup, a.steps)
+    g.synchronize()
+    got = out.cpu().numpy()
+    assert got[0] == float(nc * a.ppc) and abs(got[1] - sums[0]) <= 1e-9 * sums[0], (got, sums)
+    g.close()
+    n = nc * a.ppc
+    for name, bb in (("particles_reduce", 32), ("accelerate", 8 * 8)):
+        t = res[name].get("ms", res[name]["host_ms"])
+        res[name]["named_bytes_per_record"] = bb
+        res[name]["record_bytes"] = Kb * 8
+        res[name]["frac_of_peak_named"] = n * bb / (t / 1e3) / 1e9 / PEAK_HBM_GBS
+        res[name]["frac_of_peak_whole_records"] = n * Kb * 8 / (t / 1e3) / 1e9 / PEAK_HBM_GBS
+    res["particles"] = n
+    res["reduce_over_accelerate_host_clock"] = res["particles_reduce"]["host_ms"] / res["accelerate"]["host_ms"]
+    return res
+
+
+def main_reduce(a):
+    """The reductions of a cycle's diagnostics: one call against single-term
+    calls, field_axpy and the host way on the uniform and the refined grid,
+    and the particle reduce beside particles_accelerate."""
+    uni = measure_reduce_fields(a, False)
+    ref = measure_reduce_fields(a, True)
+    par = measure_reduce_particles(a)
+    line = {"metric": "field_reduce", "value": uni["reduce_7_terms"]["ms"], "unit": "ms", "n_gpus": 1, "steps": a.steps,
+            "warmup": a.warmup, "higher_is_better": False, "dtype": "fp64",
+            "config": {"workload": f"{a.base}^3 periodic, neighborhood 1: R = 0, and R = 1 with a z-slab of one eighth "
+                                   "refined; seven terms by volume (six squares, max |div B|); the calls alternate in "
+                                   "one run; ms: between device events, summed over a call's launches (two kernels a "
+                                   "reduce call); host_ms: the synchronized host clock; host_way: download of the seven "
+                                   f"fields and NumPy; particles: {a.ppc} records of K = 10 per cell on the uniform "
+                                   "grid, eight terms (count, charge, momenta, squares), weight -1"},
+            "bytes_per_cell": {"reduce_7_terms": "7 fields x 8 = 56 (+ 1 level byte on the refined grid)",
+                               "reduce_7_calls": "the same 56, + 1 level byte per by-volume call on the refined grid",
+                               "field_axpy": "x 8 + y 8 read, y 8 written = 24", "host_way": "56 over PCIe"},
+            "uniform": uni, "refined": ref, "particles": par}
+    txt = json.dumps(line)
+    print(txt, flush=True)
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "particles_bench_reduce.json")
     with open(out, "w") as f:
         f.write(txt + "\n")
 

@@ -1317,6 +1317,82 @@ public:
 	                const int region = DCCRGX_REGION_ALL) {
 		detail::check(dccrgx_field_axpy(g_, y.id(), a, x.id(), region));
 	}
+	// a term of field_reduce: op (DCCRGX_REDUCE_*) over a[c] * b[c], nullptr = 1.0
+	struct Field_Term {
+		int op;
+		const Device_Field<double>* a;
+		const Device_Field<double>* b;
+	};
+	// a term of particles_reduce: op over (q u) v, u and v doubles of the
+	// record or -1 for 1.0
+	struct Record_Term {
+		int op, u, v;
+	};
+	// 1 to 16 reductions over the local cells of `region` in one pass on the
+	// device; by_volume: the terms of a sum times the cell's volume;
+	// collective: combined over the processes in rank order.  Sums have a
+	// fixed order, extrema are exact (dccrgx.h has the contract).
+	std::vector<double> field_reduce(const std::vector<Field_Term>& terms, const bool by_volume = false,
+	                                 const int region = DCCRGX_REGION_ALL, const bool collective = false) {
+		const std::vector<int> t = flat(terms);
+		std::vector<double> out(terms.size());
+		detail::check(dccrgx_field_reduce(g_, t.data(), int(terms.size()), by_volume ? 1 : 0, region,
+		                                  collective ? 1 : 0, out.data()));
+		return out;
+	}
+	// the same into terms.size() doubles of device memory, queued on the
+	// compute stream: nothing waits on the host
+	void field_reduce_device(const std::vector<Field_Term>& terms, double* const device_out,
+	                         const bool by_volume = false, const int region = DCCRGX_REGION_ALL,
+	                         const bool collective = false) {
+		const std::vector<int> t = flat(terms);
+		detail::check(dccrgx_field_reduce_device(g_, t.data(), int(terms.size()), by_volume ? 1 : 0, region,
+		                                         collective ? 1 : 0, device_out));
+	}
+	// 1 to 16 reductions over the records of the local cells in one walk:
+	// {SUM, -1, -1} with weight -1 counts the records, with a weight it is the
+	// total charge, {SUM, 3, -1} the x-momentum, {MAX_ABS, 3, -1} with weight
+	// -1 max |v_x|
+	std::vector<double> particles_reduce(const Device_Variable_Field<double>& particles,
+	                                     const std::vector<Record_Term>& terms, const int record_doubles,
+	                                     const int weight_double = -1, const bool collective = false) {
+		const std::vector<int> t = flat(terms);
+		std::vector<double> out(terms.size());
+		detail::check(dccrgx_particles_reduce(g_, particles.id(), record_doubles, weight_double, t.data(),
+		                                      int(terms.size()), collective ? 1 : 0, out.data()));
+		return out;
+	}
+	void particles_reduce_device(const Device_Variable_Field<double>& particles, const std::vector<Record_Term>& terms,
+	                             double* const device_out, const int record_doubles, const int weight_double = -1,
+	                             const bool collective = false) {
+		const std::vector<int> t = flat(terms);
+		detail::check(dccrgx_particles_reduce_device(g_, particles.id(), record_doubles, weight_double, t.data(),
+		                                             int(terms.size()), collective ? 1 : 0, device_out));
+	}
+
+private:
+	static std::vector<int> flat(const std::vector<Field_Term>& terms) {
+		std::vector<int> t;
+		for (const auto& x : terms) {
+			t.push_back(x.op);
+			t.push_back(x.a ? x.a->id() : -1);
+			t.push_back(x.b ? x.b->id() : -1);
+		}
+		if (t.empty()) t.push_back(0);
+		return t;
+	}
+	static std::vector<int> flat(const std::vector<Record_Term>& terms) {
+		std::vector<int> t;
+		for (const auto& x : terms) {
+			t.push_back(x.op);
+			t.push_back(x.u);
+			t.push_back(x.v);
+		}
+		if (t.empty()) t.push_back(0);
+		return t;
+	}
+
+public:
 	// the records follow the mesh in every stop_refining: what user code does
 	// from refined_cell_data / unrefined_cell_data, on the device (a refined
 	// parent's records to the child at their position, the removed children's

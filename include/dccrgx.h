@@ -620,6 +620,65 @@ int dccrgx_divergence(dccrgx_grid* g, const int in_fields[3], int out_field, dou
                       int region);
 int dccrgx_field_axpy(dccrgx_grid* g, int y_field, double a, int x_field, int region);
 
+/* Reductions on the device: the scalars of a cycle (field energy, total
+ * charge, kinetic energy, max |v|, max |div B|) without the download of a
+ * field.  One call computes n = 1 .. 16 terms in one pass; terms holds three
+ * ints per term: the operation and two factors.  Every step is one IEEE
+ * operation.
+ * field_reduce, term j over the local cells c of `region` (DCCRGX_REGION_*;
+ * remote-copy slots are never read): t = a[c] * b[c] with a, b the fixed fp64
+ * fields terms[3 j + 1], terms[3 j + 2]; a field id of -1 stands for 1.0, so
+ * (a, -1) is a[c] itself and (-1, -1) is 1.0; a == b is a square.  With
+ * by_volume != 0 a SUM term becomes t * V_c, V_c = (lx ly) lz of
+ * dccrgx_geometry_fill's lengths, the volume the deposit's per_volume divides
+ * by, Cartesian or stretched; by_volume does not touch the other operations.
+ * particles_reduce, term j over the records p of the local cells (records of
+ * remote copies are not read): m = (q_p * u) * v, exactly
+ * dccrgx_particles_deposit_moments' m_j: q_p = record[weight_double], or 1
+ * with -1; u = record[terms[3 j + 1]], v = record[terms[3 j + 2]], doubles in
+ * [3, record_doubles) or -1 for 1.0.  Weight -1 and (-1, -1) SUM is the record
+ * count as a double, (-1, -1) SUM the total charge, (3, -1) SUM the
+ * x-momentum, (3, 3) + (4, 4) + (5, 5) twice the kinetic energy, weight -1
+ * and (3, -1) MAX_ABS max |v_x|.
+ * SUM adds the terms in an unspecified but fixed order (a function of the
+ * number of elements and of distinct fields only); no atomic decides a sum, so
+ * two calls on one state give bitwise equal results, in the host form and the
+ * device form alike.  MIN and MAX are taken over the terms, MAX_ABS over
+ * fabs(term); they are exact.  Over no elements the results are SUM +0.0,
+ * MIN +inf, MAX -inf, MAX_ABS +0.0.  A NaN among the inputs propagates through
+ * SUM per IEEE; the result of the three extrema is then unspecified (the
+ * comparisons keep their first operand on NaN).
+ * collective == 0: this process's values only (works on a detached view).
+ * collective != 0: every process calls; the processes' values are all-gathered
+ * on the device and combined in rank order (MAX_ABS as MAX), so every process
+ * gets the same bits.
+ * The _device form writes the n doubles d_out in device memory, queued on the
+ * compute stream (dccrgx_compute_stream): field_reduce_device never waits on
+ * the host (over RCCL; a host exchange function stages the collective through
+ * the host); particles_reduce_device first reads back the check of the cells'
+ * byte counts and the number of local records, as every particle call does,
+ * and waits for nothing after that.  The host form is the device form
+ * followed by one synchronising copy of n doubles: the same bits.
+ * DCCRGX_EINVAL, before any work and with the output untouched: n outside
+ * 1 .. 16, an unknown operation, a field that is variable-size or not 8 bytes
+ * wide, an invalid id other than -1, a bad region, by_volume while the grid
+ * holds a stretched geometry block without coordinates (deposit's rule),
+ * collective on several processes without a communicator, a null pointer;
+ * for particles everything deposit_moments refuses of var_field,
+ * record_doubles, the cells' byte counts, weight_double and the factors. */
+#define DCCRGX_REDUCE_SUM 0
+#define DCCRGX_REDUCE_MIN 1
+#define DCCRGX_REDUCE_MAX 2
+#define DCCRGX_REDUCE_MAX_ABS 3
+int dccrgx_field_reduce(dccrgx_grid* g, const int* terms /* 3 n: op, a_field, b_field */, int n, int by_volume,
+                        int region, int collective, double* out /* n, host */);
+int dccrgx_field_reduce_device(dccrgx_grid* g, const int* terms /* 3 n */, int n, int by_volume, int region,
+                               int collective, double* d_out /* n, device */);
+int dccrgx_particles_reduce(dccrgx_grid* g, int var_field, int record_doubles, int weight_double,
+                            const int* terms /* 3 n: op, u, v */, int n, int collective, double* out /* n, host */);
+int dccrgx_particles_reduce_device(dccrgx_grid* g, int var_field, int record_doubles, int weight_double,
+                                   const int* terms /* 3 n */, int n, int collective, double* d_out /* n, device */);
+
 /* set_send_single_cells 6677 / get_send_single_cells 6684: one message per
  * cell (tag = position + 1) instead of one per process.  On, the remote
  * neighbor updates put each cell's fixed-size payload on the wire as its own
