@@ -730,16 +730,19 @@ static void adv_fields(Grid& g, const int fids[7], const double* f[7]) {
 }
 
 // the block minima now in g.dt_part (nb of them) belong to fields fids as
-// they are now (Grid::DtCache)
+// they are now (Grid::DtCache); not kept while one of the six is external
+// (its device pointer is out: writes through it are not seen)
 static void dt_cache_set(Grid& g, const int fids[7], size_t nb) {
 	Grid::DtCache& C = g.dt_cache;
+	bool external = false;
 	for (int k = 1; k < 7; k++) {
 		C.fid[k - 1] = fids[k];
 		C.epoch[k - 1] = field(g, fids[k]).epoch;
+		external = external || field(g, fids[k]).external;
 	}
 	C.n_local = g.n_local;
 	C.nb = nb;
-	C.valid = nb > 0;
+	C.valid = nb > 0 && !external;
 }
 
 // The neighbor records of the tile sweeps (Grid::NbRecords) for the fields
@@ -2998,12 +3001,16 @@ int dccrgx_advection_initialize(dccrgx_grid* gp, const int fids[7]) {
 
 // the block minima of the time-step bound of fields fids in g.dt_part (their
 // count): the cached ones while the six velocity / length fields are
-// unwritten since (advection_adapt's reset pass leaves them), else one pass
+// unwritten since (advection_adapt's reset pass leaves them), else one pass.
+// While one of them is external (its device pointer is out, writes through
+// it are not seen) the minima are neither reused nor kept, as ensure_nbrec.
 static size_t dt_partials(Grid& g, const int fids[7]) {
 	const double* f[7];
 	adv_fields(g, fids, f);
 	Grid::DtCache& C = g.dt_cache;
-	bool ok = C.valid && C.n_local == g.n_local && C.nb > 0;
+	bool external = false;
+	for (int k = 1; k < 7; k++) external = external || field(g, fids[k]).external;
+	bool ok = !external && C.valid && C.n_local == g.n_local && C.nb > 0;
 	for (int k = 1; k < 7 && ok; k++) ok = C.fid[k - 1] == fids[k] && C.epoch[k - 1] == field(g, fids[k]).epoch;
 	if (ok) return C.nb;
 	const size_t nb = 512;

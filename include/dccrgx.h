@@ -381,7 +381,10 @@ int dccrgx_set_field_transfer(dccrgx_grid* g, int field_id, int transfer);
 int dccrgx_set_field_window(dccrgx_grid* g, int field_id, size_t offset, size_t bytes);
 /* the field's device array (slot order).  The pointer stays valid until the
  * next structural change (refinement, balance_load, loading a file).  Writes
- * made through it are seen by every call; the library's own bookkeeping of a
+ * made through it are seen by every call - the advection sweeps, their
+ * time step (dccrgx_advection_max_time_step and its device form) and
+ * dccrgx_advection_check_adaptation keep nothing derived from a field whose
+ * pointer is out; the library's own bookkeeping of a
  * field's contents (e.g. dccrgx_get_live_neighbors' record that the list
  * field's inner rows are already zero) is reset only when this function is
  * called, so a program that writes through a pointer it fetched earlier
