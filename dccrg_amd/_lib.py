@@ -143,6 +143,8 @@ _SIGS = {
     "dccrgx_curl": (C.c_int, [vp, P(C.c_int), P(C.c_int), C.c_double, C.c_int, C.c_int]),
     "dccrgx_divergence": (C.c_int, [vp, P(C.c_int), C.c_int, C.c_double, C.c_int, C.c_int]),
     "dccrgx_field_axpy": (C.c_int, [vp, C.c_int, C.c_double, C.c_int, C.c_int]),
+    "dccrgx_field_follow_mesh": (C.c_int, [vp, C.c_int, C.c_int]),
+    "dccrgx_field_follow_mode": (C.c_int, [vp, C.c_int, P(C.c_int)]),
     "dccrgx_field_reduce": (C.c_int, [vp, P(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_double)]),
     "dccrgx_field_reduce_device": (C.c_int, [vp, P(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "dccrgx_particles_reduce": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, P(C.c_int), C.c_int, C.c_int,

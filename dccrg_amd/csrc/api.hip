@@ -3246,12 +3246,18 @@ int dccrgx_advection_adapt(dccrgx_grid* gp, const int fids[7], uint64_t out[2]) 
 		// store still gets them, packed before the rebuild)
 		for (int k = 1; k < 7; k++)
 			if (fids[k] != fids[0]) field(g, fids[k]).no_carry = true;
+		// the density keeps this call's rule (a child its parent's value, a
+		// parent the mean below) whatever mode it follows the mesh with
+		const int rho_mode = field(g, fids[0]).follow_mode;
+		field(g, fids[0]).follow_mode = DCCRGX_FOLLOW_OFF;
 		try {
 			stop_refining_impl(g);
 		} catch (...) {
 			for (int k = 1; k < 7; k++) field(g, fids[k]).no_carry = false;
+			field(g, fids[0]).follow_mode = rho_mode;
 			throw;
 		}
+		field(g, fids[0]).follow_mode = rho_mode;
 		for (int k = 1; k < 7; k++) field(g, fids[k]).no_carry = false;  // no rebuild ran (nothing changed)
 		DX_LAP("adapt.1_stop_refining");
 		hipStream_t s = g.s_comp;
@@ -3465,8 +3471,29 @@ int dccrgx_gradient(dccrgx_grid* gp, int in_field, const int out_fields[3], doub
 	});
 }
 
+// cell fields follow the mesh: restriction and prolongation of a fixed fp64
+// field inside stop_refining (field_adapt.hip)
+int dccrgx_field_follow_mesh(dccrgx_grid* gp, int field_id, int mode) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		field_follow_set(g, field_id, mode);
+		return 0;
+	});
+}
+
+int dccrgx_field_follow_mode(dccrgx_grid* gp, int field_id, int* mode) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		DX_REQUIRE(mode, "null pointer");
+		const Field& f = fixed_field(g, field_id);
+		DX_REQUIRE(f.elem == 8, "a field that follows the mesh must be a fixed-size field of 8-byte elements (fp64)");
+		*mode = f.follow_mode;
+		return 0;
+	});
+}
+
 namespace {
-const char* const VC_FP64 = "the fields of a curl, divergence or axpy must be fixed-size fields of 8-byte elements (fp64)";
+const char* const VC_FP64 ="the fields of a curl, divergence or axpy must be fixed-size fields of 8-byte elements (fp64)";
 
 // the three inputs of a curl or divergence (they need not be distinct)
 void vector_inputs(Grid& g, const int in_fields[3], const double* in[3]) {

@@ -56,6 +56,15 @@ void particles_follow_set(Grid& g, int fid, int K);
 bool particles_follow_check(Grid& g, const Field& f);
 void particles_follow_rebuild(Grid& g, Field& f, const uint64_t* old_ids, size_t n_old_local, const DevMesh& newM,
                               size_t new_n_slots, size_t new_n_local, hipStream_t s);
+// cell fields follow the mesh through stop_refining (Field::follow_mode,
+// field_adapt.hip): follow_set checks and stores the mode; slope_pass, with
+// the refine set final and the old mesh still standing, leaves Grid::fslopes
+// for the LINEAR fields (nothing when there is none or nothing is refined);
+// follow_restrict, after the rebuild, gives the merged parents of the fields
+// `fids` their children's mean or sum from the removed store
+void field_follow_set(Grid& g, int fid, int mode);
+void field_slope_pass(Grid& g, const uint64_t* refined_dev, size_t n_refined);
+void field_follow_restrict(Grid& g, const std::vector<int>& fids);
 // particles <-> cell fields with the weight W(p, c) of dccrgx.h (shape 0 NGP,
 // 1 CIC over leaves): deposit sums q W over the records of a local cell and
 // of the distinct leaves of its neighbors_of into a fixed fp64 field; gather

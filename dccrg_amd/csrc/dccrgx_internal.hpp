@@ -341,6 +341,11 @@ struct Field {
 	// adapt_stats = {to children, to parents, lost} of the last one
 	int follow_K = 0;
 	uint64_t adapt_stats[3] = {0, 0, 0};
+	// a fixed fp64 cell field follows the mesh (field_adapt.hip):
+	// DCCRGX_FOLLOW_* (0: off), kept until changed; follow_lin is the field's
+	// row in Grid::fslopes during a stop_refining (-1: none)
+	int follow_mode = 0;
+	int follow_lin = -1;
 	bool full_window() const { return win_off == 0 && win_len == elem; }
 };
 
@@ -624,6 +629,24 @@ struct Grid {
 	// the rebuild in progress is stop_refining's: a following field's records
 	// go to the new children and the new parents (particles_follow_rebuild)
 	bool adapting = false;
+	// cell fields follow the mesh (field_adapt.hip): the rebuild in progress
+	// is stop_refining's and `fslopes` holds what its slope pass left for the
+	// carry step: per LINEAR field j and refined cell i of the list (all
+	// processes' refined cells; rows of cells that are not local stay
+	// unwritten) the limited half-differences t_d at t[(3 j + d) n + i], and
+	// for the old local slot of every refined local cell its i in ppos (the
+	// other slots unwritten: read only through a child's source slot)
+	bool field_adapting = false;
+	struct FieldSlopes {
+		DBuf<double> t;
+		DBuf<int32_t> ppos;
+		size_t n = 0;
+		void clear() {
+			t.release();
+			ppos.release();
+			n = 0;
+		}
+	} fslopes;
 	Migration mig;
 	// the range map over the full id range of every level (one process,
 	// Morton-ordered own leaves: rebuild's "direct" mode), kept across
@@ -1167,8 +1190,37 @@ void k_adv_bands(const MapCtx& m, const double* rho, const FaceView& F, const ui
 // process: exactly the removed cells' parents; used when 8 np removed cells)
 void k_adv_merge_parents(const MapCtx& m, const DevMesh& dm, size_t n_local, LazyIds& rm, double* rho,
                          const double* removed_rho, hipStream_t s, const uint64_t* parents = nullptr, size_t np = 0);
-void k_adv_parent_density(double* rho, const int32_t* parent_slot, const int32_t* child_idx, const double* removed_rho,
-                          size_t np, hipStream_t s);
+// ---- cell fields follow the mesh (field_adapt.hip) --------------------------
+// up to kFollowBatch fp64 fields of one restriction launch: the new array,
+// the removed store and the mode (DCCRGX_FOLLOW_*) of each
+constexpr int kFollowBatch = 8;
+struct FollowSet {
+	int n = 0;
+	double* data[kFollowBatch];
+	const double* removed[kFollowBatch];
+	int mode[kFollowBatch];
+};
+// the rows of the merged families from the removed store's ids `rm` (store
+// order): parents grouped (given sorted when known, see k_adv_merge_parents),
+// cidx[8 i + k] = the store index of child k (ascending id) of parent i,
+// pslot[i] = the parent's local slot; every row is checked complete
+size_t k_merged_rows(const MapCtx& m, const DevMesh& dm, size_t n_local, LazyIds& rm, const uint64_t* parents,
+                     size_t np_given, DBuf<int32_t>& cidx, DBuf<int32_t>& pslot, hipStream_t s);
+// data[j][pslot[i]] = the mean (acc += c_k / 8.0; MEAN, LINEAR) or the sum
+// (SUM) of the eight removed children, ascending id, for all fields of F
+void k_field_merge_parents(const FollowSet& F, const int32_t* pslot, const int32_t* cidx, size_t np, hipStream_t s);
+// the slope pass over the n refined cells `refined` (old local slot pslot[i],
+// skipped where it is none or no local slot): t_d of the nlin old arrays in,
+// and ppos[pslot[i]] = i
+void k_field_slopes(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
+                    const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine, size_t n_local,
+                    const int32_t* pslot, size_t n, const double* const* in, int nlin, double* t, int32_t* ppos,
+                    hipStream_t s);
+// rebuild step 6 for a field that follows with SUM or LINEAR: k_gather_rows
+// with the child rule where a new local slot's source is a coarser old cell
+void k_field_follow_gather(const MapCtx& m, const double* old_data, const int32_t* src, size_t n_slots, size_t n_local,
+                           const uint64_t* slot_ids, const uint64_t* old_slot_ids, int mode, const double* t,
+                           const int32_t* ppos, size_t n_ppos, size_t n_refined, double* out, hipStream_t s);
 // (dt_partial: when given, the block minima of the time-step bound of the
 // values written, as k_adv_dt computes them; returns their count)
 constexpr unsigned kDtPartials = 2048;  // block minima a reset pass leaves at most

@@ -889,18 +889,41 @@ void stop_refining_impl(Grid& g) {
 		nm.n_prefix = pos_at[1];
 	}
 	DX_LAP("sr.6_apply");
+	// cell fields that follow the mesh (field_adapt.hip): the fields this call
+	// treats (a no_carry field keeps its caller's rule), and the slopes of the
+	// LINEAR ones from the old mesh and the old values while both still stand
+	std::vector<int> ffollow;
+	for (size_t k = 0; k < g.fields.size(); k++) {
+		const Field& f = g.fields[k];
+		if (!f.var && f.follow_mode != DCCRGX_FOLLOW_OFF && !f.no_carry) ffollow.push_back(int(k));
+	}
+	if (!ffollow.empty() && !S.empty()) {
+		field_slope_pass(g, dS.p, S.size());
+		DX_LAP("sr.6b_field_slopes");
+	}
 	g.adapting = following;
+	g.field_adapting = !ffollow.empty();
+	auto done = [&g] {
+		g.adapting = false;
+		g.field_adapting = false;
+		g.fslopes.clear();
+		for (auto& f : g.fields) f.follow_lin = -1;
+	};
 	try {
 		rebuild(g, nm);
 	} catch (...) {
-		g.adapting = false;
+		done();
 		throw;
 	}
-	g.adapting = false;
+	done();
 	DX_LAP("sr.7_rebuild");
 	if (g.size == 1 && !F.empty()) {
 		g.merged_dev = std::move(dF);
 		g.n_merged = F.size();
+	}
+	if (!ffollow.empty() && !F.empty()) {
+		field_follow_restrict(g, ffollow);
+		DX_LAP("sr.8_field_restrict");
 	}
 }
 

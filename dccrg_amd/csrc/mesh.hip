@@ -638,6 +638,17 @@ void rebuild(Grid& g, Mesh& nm) {
 		nd.alloc(g.n_slots * f.elem);
 		if (f.no_carry && nd.n) {
 			if (g.n_slots > nl) HIP_CHECK(hipMemsetAsync(nd.p + nl * f.elem, 0, (g.n_slots - nl) * f.elem, s));
+		} else if (f.data.p && old_slot_ids.p && g.field_adapting && f.elem == 8 &&
+		           (f.follow_mode == DCCRGX_FOLLOW_SUM || (f.follow_mode == DCCRGX_FOLLOW_LINEAR && f.follow_lin >= 0))) {
+			// a field that follows the mesh through stop_refining: the gather
+			// with the child rule where the source is the cell's parent (MEAN's
+			// child is the plain copy below)
+			const bool lin = f.follow_mode == DCCRGX_FOLLOW_LINEAR;
+			const size_t np = g.fslopes.n;
+			k_field_follow_gather(m, reinterpret_cast<const double*>(f.data.p), src.p, g.n_slots, nl, g.slot_ids.p,
+			                      old_slot_ids.p, f.follow_mode,
+			                      lin ? g.fslopes.t.p + size_t(3) * size_t(f.follow_lin) * np : nullptr,
+			                      g.fslopes.ppos.p, g.fslopes.ppos.n, np, reinterpret_cast<double*>(nd.p), s);
 		} else if (f.data.p && old_slot_ids.p) {
 			k_gather_rows(f.data.p, src.p, g.n_slots, f.elem, nd.p, s);  // zeros where no source
 		} else if (nd.n) {

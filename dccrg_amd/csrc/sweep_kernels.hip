@@ -1957,59 +1957,6 @@ __global__ void gather_ids_bands_kernel(const uint64_t* __restrict__ ids, const 
 	}
 }
 
-// adapt_grid (adapter.hpp:260-290): a merged parent's density is the sum of
-// its removed children's densities / 8 (children in ascending id)
-__global__ void adv_parent_density_kernel(double* __restrict__ rho, const int32_t* __restrict__ parent_slot,
-                                          const int32_t* __restrict__ child_idx, const double* __restrict__ removed_rho,
-                                          size_t np) {
-#pragma clang fp contract(off)
-	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < np; i += size_t(gridDim.x) * blockDim.x) {
-		double acc = 0;
-		for (int k = 0; k < 8; k++) acc += removed_rho[child_idx[8 * i + k]] / 8;
-		rho[parent_slot[i]] = acc;
-	}
-}
-
-// merged families on the device: the parent of every removed child, and
-// (after the parents are sorted and deduplicated) each child's place in its
-// parent's row of eight, in map_all_children order (= ascending id)
-__global__ void removed_parents_kernel(MapCtx m, const uint64_t* __restrict__ rm, size_t n, uint64_t* __restrict__ par) {
-	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x)
-		par[i] = map_parent(m, rm[i]);
-}
-
-__global__ void removed_rows_kernel(MapCtx m, const uint64_t* __restrict__ rm, size_t n,
-                                    const uint64_t* __restrict__ parents, size_t np, int32_t* __restrict__ cidx,
-                                    int* __restrict__ err) {
-	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
-		uint64_t x, y, z;
-		const int l = map_indices(m, rm[i], x, y, z);
-		const uint64_t p = map_parent(m, rm[i]);
-		size_t lo = 0, hi = np;
-		while (lo < hi) {
-			const size_t mid = (lo + hi) / 2;
-			if (parents[mid] < p) lo = mid + 1;
-			else hi = mid;
-		}
-		if (l <= 0 || lo >= np || parents[lo] != p) {
-			atomicOr(err, 1);
-			continue;
-		}
-		const uint64_t o = uint64_t(1) << (m.R - l);  // the child's length in indices
-		const int k = int((x / o) & 1u) | int(((y / o) & 1u) << 1) | int(((z / o) & 1u) << 2);
-		cidx[8 * lo + size_t(k)] = int32_t(i);
-	}
-}
-
-__global__ void check_rows_kernel(const int32_t* __restrict__ cidx, const int32_t* __restrict__ pslot, size_t np,
-                                  size_t n_local, int* __restrict__ err) {
-	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < np; i += size_t(gridDim.x) * blockDim.x) {
-		if (pslot[i] < 0 || size_t(pslot[i]) >= n_local) atomicOr(err, 2);
-		for (int k = 0; k < 8; k++)
-			if (cidx[8 * i + k] < 0) atomicOr(err, 4);
-	}
-}
-
 // adapt_grid (adapter.hpp:294-305): velocity (solve.hpp:336-342) and lengths
 // (Cartesian_Geometry get_center / get_length, dccrg_cartesian_geometry.hpp:
 // 282-362) of every local cell
@@ -2408,49 +2355,16 @@ void k_adv_bands(const MapCtx& m, const double* rho, const FaceView& F, const ui
 void k_adv_merge_parents(const MapCtx& m, const DevMesh& dm, size_t n_local, LazyIds& rm, double* rho,
                          const double* removed_rho, hipStream_t s, const uint64_t* parents, size_t np_given) {
 	if (rm.empty()) return;
-	const size_t n = rm.size();
-	DBuf<uint64_t> up, par;
-	const uint64_t* rm_dev = rm.dev();
-	if (!rm_dev) {
-		upload(up, rm.host(s), s);
-		rm_dev = up.p;
-	}
-	size_t np = np_given;
-	const uint64_t* parp = parents;
-	if (!(parents && np * 8 == n)) {
-		// the parents of the removed cells (the families' parents as
-		// stop_refining merged them, when given: sorted and unique, and
-		// removed_rows / check_rows below still verify every child maps to one)
-		par.alloc(n);
-		removed_parents_kernel<<<grid_for(n, 256), 256, 0, s>>>(m, rm_dev, n, par.p);
-		HIP_CHECK(hipGetLastError());
-		np = sort_unique_u64(par.p, n, s, map_id_bits(m));
-		parp = par.p;
-	}
-	DX_REQUIRE(np * 8 == n, "a merged family's removed children are incomplete");
+	// the rows and the kernel of the fields that follow the mesh
+	// (field_adapt.hip): one copy of the mean's arithmetic
 	DBuf<int32_t> cidx, pslot;
-	DBuf<int> err;
-	cidx.alloc(8 * np);
-	pslot.alloc(np);
-	err.alloc(1);
-	HIP_CHECK(hipMemsetAsync(cidx.p, 0xff, 8 * np * sizeof(int32_t), s));
-	HIP_CHECK(hipMemsetAsync(err.p, 0, sizeof(int), s));
-	removed_rows_kernel<<<grid_for(n, 256), 256, 0, s>>>(m, rm_dev, n, parp, np, cidx.p, err.p);
-	HIP_CHECK(hipGetLastError());
-	k_lookup_slots(parp, np, dm, pslot.p, err.p, s);  // a missing parent sets err too
-	check_rows_kernel<<<grid_for(np, 256), 256, 0, s>>>(cidx.p, pslot.p, np, n_local, err.p);
-	HIP_CHECK(hipGetLastError());
-	int h = 0;
-	d2h_small(&h, err.p, sizeof(int), s);
-	DX_REQUIRE(h == 0, "merged parent is not local or a removed child's payload is missing");
-	k_adv_parent_density(rho, pslot.p, cidx.p, removed_rho, np, s);
-}
-
-void k_adv_parent_density(double* rho, const int32_t* parent_slot, const int32_t* child_idx, const double* removed_rho,
-                          size_t np, hipStream_t s) {
-	if (!np) return;
-	adv_parent_density_kernel<<<grid_for(np, 256), 256, 0, s>>>(rho, parent_slot, child_idx, removed_rho, np);
-	HIP_CHECK(hipGetLastError());
+	const size_t np = k_merged_rows(m, dm, n_local, rm, parents, np_given, cidx, pslot, s);
+	FollowSet F;
+	F.n = 1;
+	F.data[0] = rho;
+	F.removed[0] = removed_rho;
+	F.mode[0] = DCCRGX_FOLLOW_MEAN;
+	k_field_merge_parents(F, pslot.p, cidx.p, np, s);
 }
 
 static void k_gather_ids_bands(const uint64_t* ids, const uint8_t* band, const uint32_t* at, size_t n, uint64_t* oid,

@@ -925,6 +925,29 @@ class Dccrg:
         record_doubles=0 turns it off again (the default: new cells empty)."""
         check(lib().dccrgx_particles_follow_mesh(self.h, field.id, int(record_doubles)))
 
+    FOLLOW = {None: 0, "off": 0, "mean": 1, "sum": 2, "linear": 3}
+
+    def field_follow_mesh(self, field, mode):
+        """The fixed float64 cell field `field` follows the mesh in every
+        stop_refining (advection_adapt's included), on the device.  mode
+        "mean": an intensive quantity (a merged parent takes its children's
+        mean, a new child its parent's value); "sum": an extensive one (the
+        children's sum, an eighth of the parent's value); "linear": the mean,
+        and children by a conservative, bound-preserving linear prolongation
+        built on gradient()'s derivative of the old mesh (update the copies of
+        remote neighbors first).  None turns it off again (the default: a
+        child is a copy, a merged parent zero).  The mode holds until it is
+        changed."""
+        if mode not in self.FOLLOW:
+            raise ValueError(f"mode must be None, 'mean', 'sum' or 'linear', not {mode!r}")
+        check(lib().dccrgx_field_follow_mesh(self.h, field.id, self.FOLLOW[mode]))
+
+    def field_follow_mode(self, field):
+        """The mode set by field_follow_mesh: None, "mean", "sum" or "linear"."""
+        m = C.c_int(0)
+        check(lib().dccrgx_field_follow_mode(self.h, field.id, C.byref(m)))
+        return (None, "mean", "sum", "linear")[m.value]
+
     def particles_adapt_stats(self, field):
         """This process's counts of the last stop_refining for a following field."""
         st = (C.c_uint64 * 3)()

@@ -16,6 +16,13 @@ records the parent commit's Cartesian lines given with --parent.
 one eighth of the cells is refined and merged again, and the two stop_refining
 calls are timed with follow on and off, beside one re-lay of the pool.
 
+--fields-adapt measures what it costs that fp64 cell fields follow the mesh
+(Dccrg.field_follow_mesh) in --adapt's scenario: stop_refining with no cell
+field (the parent commit's --adapt follow-off scenario, given with --parent),
+with 1 and 6 fields that are only carried, that follow as MEAN and that follow
+as LINEAR, alternating, and the host way (download the fields and the removed
+store, the NumPy mean, upload) beside them.
+
 --deposit measures the particle <-> mesh transfer on the same grid: CIC and
 NGP Dccrg.particles_deposit (K = 4) and a CIC Dccrg.particles_gather of three
 fields (K = 7), beside the default step and re-lay in the same run.
@@ -169,6 +176,11 @@ def main(argv=None):
                    help="particles following the mesh: a z-slab of a base^3, R = 1 grid refined and merged again, "
                         "stop_refining with follow on against follow off (--repeats of each, alternating) and "
                         "against one re-lay of the pool; writes profiles/particles_bench_adapt.json unless --out")
+    p.add_argument("--fields-adapt", action="store_true",
+                   help="cell fields following the mesh (Dccrg.field_follow_mesh): on --adapt's grid stop_refining with "
+                        "0, 1 and 6 fp64 fields carried only, following as MEAN and as LINEAR (--repeats of each, "
+                        "alternating), the host way beside them, and with --parent the parent commit's --adapt "
+                        "follow-off runs; writes profiles/particles_bench_fields_adapt.json unless --out")
     p.add_argument("--deposit", action="store_true",
                    help="charge deposition and field gather: CIC and NGP particles_deposit (K = 4) and a CIC "
                         "particles_gather of three fields (K = 7) beside the particle step and the re-lay in the "
@@ -209,6 +221,8 @@ def main(argv=None):
         return main_moments(a)
     if a.deposit:
         return main_deposit(a)
+    if a.fields_adapt:
+        return main_fields_adapt(a)
     if a.adapt:
         return main_adapt(a)
     if a.stretched:
@@ -376,6 +390,137 @@ def main_adapt(a):
     print(txt, flush=True)
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                 "particles_bench_adapt.json")
+    with open(out, "w") as f:
+        f.write(txt + "\n")
+
+
+def measure_fields_adapt(a, nf, mode, host=False):
+    """measure_adapt(follow=False)'s scenario - the same grid, the same
+    particle field, the same slab refined and merged again - with nf more
+    fp64 cell fields that follow the mesh with `mode` (None: they are only
+    carried).  host=True (mode None) also times the host way after the merge:
+    download every field and its removed store, the NumPy mean per merged
+    parent, upload."""
+    import dccrg_amd
+    from dccrg_amd._lib import check, lib
+
+    n = a.base
+    g = dccrg_amd.Dccrg(0, 1, 0).set_initial_length((n, n, n)).set_neighborhood_length(1)
+    g.set_maximum_refinement_level(1).set_periodic(True, True, True).initialize()
+    fld = g.add_variable_field("particles", np.float64, True)
+    ids = g.slot_ids()[: g.n_local]
+    nc = ids.size
+    k = (ids - np.uint64(1)).astype(np.int64)
+    ix = np.stack([k % n, (k // n) % n, k // (n * n)], axis=1)
+    rng = np.random.default_rng(1)
+    pos = (ix.astype(np.float64)[:, None, :] + rng.random((nc, a.ppc, 3))).reshape(-1)
+    fld.resize(np.full(nc, a.ppc * K, np.uint64))
+    check(lib().dccrgx_variable_field_upload(g.h, fld.id, 0, nc, pos.ctypes.data_as(C.c_void_p), pos.nbytes))
+    del pos
+    fields = []
+    for j in range(nf):
+        f = g.add_field(f"f{j}", np.float64, True)
+        f.set(rng.random(g.n_slots))
+        g.field_follow_mesh(f, mode)
+        fields.append(f)
+    first = fields[0].get(0, nc) if fields else None
+
+    def timed_stop_refining():
+        g.synchronize()
+        t0 = time.perf_counter()
+        g.stop_refining()
+        g.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    slab = ids[ix[:, 2] < max(n // 8, 1)]
+    for c in slab:
+        g.refine_completely(int(c))
+    refine_ms = timed_stop_refining()
+    for c in g.mapping_batch(slab)["child"]:
+        g.unrefine_completely(int(c))
+    unrefine_ms = timed_stop_refining()
+    assert g.n_local == nc, (g.n_local, nc)
+    out = dict(fields=nf, mode=mode or "off", refine_ms=refine_ms, unrefine_ms=unrefine_ms, cells=int(nc),
+               refined_parents=int(slab.size))
+    if host:
+        g.synchronize()
+        t0 = time.perf_counter()
+        rm = g.get_removed_cells()
+        par, inv = np.unique(g.mapping_batch(rm)["parent"], return_inverse=True)
+        sl = g.slot_ids()[:nc]
+        order = np.argsort(sl)
+        at = order[np.searchsorted(sl[order], par)]
+        for f in fields:
+            v = f.get(0, nc)
+            v[at] = np.bincount(inv, weights=f.get_removed() / 8.0, minlength=par.size)
+            f.set(v)
+        g.synchronize()
+        out["host_unrefine_ms"] = (time.perf_counter() - t0) * 1e3
+        mode = "mean"  # what the fields now hold
+    if fields and mode:
+        # SUM of eighths, MEAN of copies and LINEAR's conservative children all give the parent back
+        got = fields[0].get(0, nc)
+        assert np.allclose(got, first, rtol=1e-13, atol=1e-15), float(np.max(np.abs(got - first)))
+    g.close()
+    return out
+
+
+def main_fields_adapt(a):
+    """stop_refining with 0, 1 and 6 fp64 cell fields, carried only, following
+    as MEAN and following as LINEAR, alternating, each on a fresh grid; the
+    host way beside them; the parent commit's follow-off runs when given."""
+    configs = [("off_0", 0, None), ("off_1", 1, None), ("off_6", 6, None), ("mean_1", 1, "mean"),
+               ("mean_6", 6, "mean"), ("linear_1", 1, "linear"), ("linear_6", 6, "linear")]
+    runs = {name: [] for name, _, _ in configs}
+    measure_fields_adapt(a, 1, "linear")  # warm-up: code objects, the pool's first blocks
+    for _ in range(max(a.repeats, 1)):
+        for name, nf, mode in configs:
+            runs[name].append(measure_fields_adapt(a, nf, mode, host=mode is None and nf > 0))
+    W = ("refine_ms", "unrefine_ms")
+    med = {k: {w: float(np.median([r[w] for r in v])) for w in W} for k, v in runs.items()}
+    spread = {k: {w: [min(r[w] for r in v), max(r[w] for r in v)] for w in W} for k, v in runs.items()}
+    host = {nf: float(np.median([r["host_unrefine_ms"] for r in runs[f"off_{nf}"]])) for nf in (1, 6)}
+    added = {}
+    for mode in ("mean", "linear"):
+        for nf in (1, 6):
+            d = {w: med[f"{mode}_{nf}"][w] - med[f"off_{nf}"][w] for w in W}
+            added[f"{mode}_{nf}"] = {
+                "refine_ms": d["refine_ms"], "unrefine_ms": d["unrefine_ms"],
+                "refine_over_off_0": d["refine_ms"] / med["off_0"]["refine_ms"],
+                "unrefine_over_off_0": d["unrefine_ms"] / med["off_0"]["unrefine_ms"],
+                "host_unrefine_over_added_unrefine": host[nf] / d["unrefine_ms"] if d["unrefine_ms"] > 0 else None}
+    r0 = runs["off_0"][0]
+    line = {"metric": "field_follow_mesh", "value": added["linear_6"]["refine_ms"], "unit": "ms", "n_gpus": 1,
+            "higher_is_better": False, "dtype": "fp64",
+            "config": {"workload": f"{a.base}^3 periodic, R = 1, neighborhood 1, {a.ppc} particles per cell (not "
+                                   f"following), K = {K}; a z-slab of one eighth of the cells refined by one "
+                                   "stop_refining, the same families merged by the next; a fresh grid per run, the "
+                                   "configurations alternating",
+                       "cells": r0["cells"], "refined_parents": r0["refined_parents"], "repeats": a.repeats},
+            "stop_refining_ms": med, "spread_ms": spread, "runs": runs,
+            "added_by_following": {"what": "median stop_refining with the fields following minus with the same "
+                                           "fields only carried; over off_0: as a multiple of stop_refining "
+                                           "without any cell field", **added},
+            "host_way": {"what": "after the merge: get_removed_cells, every field and its removed store downloaded, "
+                                 "the mean per merged parent in NumPy, every field uploaded",
+                         "unrefine_ms": host},
+            "slope_pass": "a list pass over the refined parents (field_slopes_kernel), not the full-grid gradient"}
+    if a.parent:
+        pr = []
+        for path in a.parent.split(","):
+            with open(path) as f:
+                pr += [json.loads(ln) for ln in f if ln.strip()]
+        pr = [r for ln in pr for r in (ln["follow_off"]["runs"] if "follow_off" in ln else [ln])]
+        line["parent_follow_off"] = {
+            "what": "the parent commit's stop_refining of off_0's scenario, same machine visit",
+            "refine_ms": float(np.median([r["refine_ms"] for r in pr])),
+            "unrefine_ms": float(np.median([r["unrefine_ms"] for r in pr])),
+            "refine_ms_spread": [min(r["refine_ms"] for r in pr), max(r["refine_ms"] for r in pr)],
+            "unrefine_ms_spread": [min(r["unrefine_ms"] for r in pr), max(r["unrefine_ms"] for r in pr)], "runs": pr}
+    txt = json.dumps(line)
+    print(txt, flush=True)
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "particles_bench_fields_adapt.json")
     with open(out, "w") as f:
         f.write(txt + "\n")
 

@@ -1400,6 +1400,24 @@ public:
 	void particles_follow_mesh(const Device_Variable_Field<double>& particles, const int record_doubles = 3) {
 		detail::check(dccrgx_particles_follow_mesh(g_, particles.id(), record_doubles));
 	}
+	// a fixed fp64 cell field follows the mesh in every stop_refining: what
+	// user code does from refined_cell_data / unrefined_cell_data, on the
+	// device.  mode DCCRGX_FOLLOW_MEAN (an intensive quantity: a merged parent
+	// takes its removed children's mean, a new child its parent's value), _SUM
+	// (an extensive one: the children's sum, an eighth of the parent's value),
+	// _LINEAR (the mean, and children by a conservative, bound-preserving
+	// linear prolongation on gradient()'s derivative of the old mesh: update
+	// the copies of remote neighbors first); DCCRGX_FOLLOW_OFF turns it off
+	// again (a child a copy, a merged parent default-constructed)
+	void field_follow_mesh(const Device_Field<double>& field, const int mode) {
+		detail::check(dccrgx_field_follow_mesh(g_, field.id(), mode));
+	}
+	// the mode field_follow_mesh set (DCCRGX_FOLLOW_*)
+	int field_follow_mode(const Device_Field<double>& field) const {
+		int mode = DCCRGX_FOLLOW_OFF;
+		detail::check(dccrgx_field_follow_mode(g_, field.id(), &mode));
+		return mode;
+	}
 	// {to children, to parents, lost} of this process in the last stop_refining
 	std::array<uint64_t, 3> particles_adapt_stats(const Device_Variable_Field<double>& particles) const {
 		std::array<uint64_t, 3> st{{0, 0, 0}};

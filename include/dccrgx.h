@@ -623,6 +623,56 @@ int dccrgx_divergence(dccrgx_grid* g, const int in_fields[3], int out_field, dou
                       int region);
 int dccrgx_field_axpy(dccrgx_grid* g, int y_field, double a, int x_field, int region);
 
+/* Cell fields follow the mesh.  The reference gives a new child a copy of its
+ * parent's payload and leaves the parent of a merged family default-
+ * constructed (execute_refines 10104-10554; the user is handed
+ * refined_cell_data and unrefined_cell_data).  With a mode other than OFF every
+ * dccrgx_stop_refining, the one inside dccrgx_advection_adapt and induced
+ * refines included, restricts and prolongs the local cells of the fixed fp64
+ * field field_id itself, on the device.  The mode is per field, starts OFF and
+ * holds until it is changed: it survives stop_refining, balance_load and
+ * grid-file loads.  Every product, quotient, sum and difference below is one
+ * IEEE fp64 operation in the stated order (no contraction).
+ *   DCCRGX_FOLLOW_OFF     the behaviour described above, bit for bit
+ *   DCCRGX_FOLLOW_MEAN    an intensive quantity (phi, E, B, a density)
+ *   DCCRGX_FOLLOW_SUM     an extensive quantity (a charge or a count per cell)
+ *   DCCRGX_FOLLOW_LINEAR  MEAN's restriction, limited linear prolongation
+ * Merged parent: its eight children c_0 .. c_7 in ascending id, their payloads
+ * from the removed store (which holds the children of other processes too and
+ * answers as before).  MEAN and LINEAR: acc = 0; for k: acc = acc + c_k / 8.0.
+ * SUM: acc = 0; for k: acc = acc + c_k.  Children are of equal volume under
+ * both geometries (a stretched level-0 cell is split evenly), so the plain mean
+ * is the volume-weighted one.
+ * New child of a refined local parent of value v.  MEAN: v.  SUM: v * 0.125.
+ * LINEAR, from the old mesh and the old values, the field's remote copies
+ * included (update them first, as for dccrgx_gradient): for d = 0, 1, 2,
+ * g_d = the value `grad` of dccrgx_gradient's contract for this field, cell and
+ * dimension, before the scaling; q_d = L_d * 0.25 with L_d the length that
+ * contract uses; e_d = g_d * q_d.  Delta = (|e_0| + |e_1|) + |e_2|.  m and M
+ * are the minimum and the maximum of v and of the value of every face-neighbor
+ * leaf of the parent: each of the four cells of a finer face counts on its own,
+ * a missing side counts for nothing.  alpha = 1.0; if Delta > 0:
+ * up = (M - v) / Delta; dn = (v - m) / Delta; alpha = min(1.0, min(up, dn)).
+ * t_d = alpha * e_d.  Child k in ascending id has b_d = bit d of k and
+ * s_d = +1 if b_d is set, -1 otherwise; its value is
+ * ((v + s_0 t_0) + s_1 t_1) + s_2 t_2.
+ * Consequences: a local extremum is injected (alpha = 0), and so is a cell
+ * whose only neighbor along the one direction of variation is missing at an
+ * open edge; the children stay inside [m, M] up to rounding, so a non-negative
+ * field stays non-negative; the mean of the eight children is v up to rounding.
+ * Everything else is as with OFF: cells that stay keep their bits, remote-copy
+ * slots are carried as before (update them before reading them), a field the
+ * call itself rewrites (dccrgx_advection_adapt's density, velocities and
+ * lengths) keeps that call's rule whatever its mode.
+ * DCCRGX_EINVAL: a variable-size field, a field that is not 8 bytes wide, a bad
+ * field id, a bad mode. */
+#define DCCRGX_FOLLOW_OFF 0
+#define DCCRGX_FOLLOW_MEAN 1
+#define DCCRGX_FOLLOW_SUM 2
+#define DCCRGX_FOLLOW_LINEAR 3
+int dccrgx_field_follow_mesh(dccrgx_grid* g, int field_id, int mode);
+int dccrgx_field_follow_mode(dccrgx_grid* g, int field_id, int* mode);
+
 /* Reductions on the device: the scalars of a cycle (field energy, total
  * charge, kinetic energy, max |v|, max |div B|) without the download of a
  * field.  One call computes n = 1 .. 16 terms in one pass; terms holds three
