@@ -2492,6 +2492,17 @@ int dccrgx_particles_boris(dccrgx_grid* gp, int var_field, int record_doubles, i
 	});
 }
 
+int dccrgx_particles_create(dccrgx_grid* gp, int var_field, int record_doubles, int count_field, double count,
+                            int round_random, const int* recipe_i, const double* recipe_d, uint64_t seed,
+                            uint64_t* created) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		particles_create(g, var_field, record_doubles, count_field, count, round_random, recipe_i, recipe_d, seed,
+		                 created);
+		return 0;
+	});
+}
+
 // cells_to_send / cells_to_receive while a balance_load is in progress
 // (initialize_balance_load fills them with the migration lists, 3746-3884)
 int dccrgx_get_migration_cells(dccrgx_grid* gp, int peer, int incoming, uint64_t* ids, size_t cap, size_t* n) {

@@ -83,6 +83,11 @@ void particles_deposit_moments(Grid& g, int fid, int K, int shape, int weight_do
 // the Boris kick of dccrgx.h with E at e_first .., B at b_first ..,
 // h = factor q, for every record of a local cell
 void particles_boris(Grid& g, int fid, int K, int e_first, int b_first, int weight_double, double factor);
+// dccrgx_particles_create: n_c new records behind every local cell's own,
+// every value a function of (seed, cell id, index, double); *created: their
+// number on this process
+void particles_create(Grid& g, int fid, int K, int count_field, double count, int round_random, const int* recipe_i,
+                      const double* recipe_d, uint64_t seed, uint64_t* created);
 // n reductions terms[3 j] (DCCRGX_REDUCE_*) over (q * record[terms[3 j + 1]]) *
 // record[terms[3 j + 2]] (-1: 1.0) of the local cells' records into the device
 // doubles d_out, queued on the compute stream; collective: combined over the

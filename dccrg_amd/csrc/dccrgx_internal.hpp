@@ -1238,6 +1238,11 @@ uint64_t var_total(const Field& f, size_t n_slots, hipStream_t s);
 void var_sizes(const Field& f, const int32_t* slots, size_t slot0, size_t n, uint64_t* out, hipStream_t s);
 // new sizes for every slot (device): each keeps its first min(old, new) bytes, the rest zero
 void var_resize(Field& f, size_t n_slots, const uint64_t* new_sizes, hipStream_t s);
+// its re-lay: a fresh pool of `total` bytes at the offsets noff (n_slots + 1,
+// the scan of the new sizes), each slot's first min(old, new) bytes copied,
+// the rest zeroed or, zero == false, left for the caller to write; swapped in
+// with s drained, noff then holds the previous offsets
+void var_relay(Field& f, size_t n_slots, DBuf<uint64_t>& noff, uint64_t total, bool zero, hipStream_t s);
 // the payloads of slots[0..n): sizes and concatenated bytes; returns the byte total
 size_t var_gather(const Field& f, const int32_t* slots, size_t n, DBuf<uint64_t>& sizes, DBuf<uint8_t>& bytes,
                   hipStream_t s);

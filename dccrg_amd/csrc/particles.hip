@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "dccrgx_grid.hpp"
+#include "dccrgx_philox.hpp"
 #include "dccrgx_reduce.hpp"
 
 // x + v dt, x +- L ceil(d / L) and (x - start) / l are separately rounded
@@ -1956,6 +1957,331 @@ RedVolume reduce_volume(Grid& g, bool by_volume) {
 		V.slot_lvl = g.slot_lvl.p;
 	}
 	return V;
+}
+
+// ---------------------------------------------------------------------------
+// Particles are created on the device (dccrgx_particles_create; DESIGN.md
+// "Particles").  Every value is a function of (seed, cell id, index among the
+// cell's new records, double): Philox4x32-10 keyed by the seed with that
+// counter, so neither the slot, the launch nor the other processes matter.
+//   1. counts   - a thread per slot: the new byte size (old + 8 K n_c of a
+//                 local cell, old of a remote copy), the two refusals;
+//   2. a scan of the sizes and the re-lay of varfield.hip, old records in
+//                 front, the new region left unwritten;
+//   3. generate - a thread per *double* of the new records: a wave stores 512
+//                 contiguous bytes wherever it lies inside one cell.  The
+//                 cell comes from the new records' offsets by the locate
+//                 kernel's narrowed search.  No atomic, no exchange: doubles
+//                 0 and 1 each compute block 0.
+namespace {
+
+constexpr int kCB = 256;  // doubles per block pass
+
+struct CRecipe {
+	const double *fa, *fb;  // cell fields scaling a and b (nullptr: none)
+	double a, b;
+	int kind;  // 0 constant, 1 uniform, 2 normal
+};
+
+// geometry_fill_kernel's geometry: Cartesian start and l0, or the packed
+// coordinates of the stretched one
+struct CGeo {
+	double start[3], l0[3];
+	const double* c;
+	uint32_t off[3];
+};
+
+struct CArgs {
+	double* pool;
+	const uint64_t* noff;        // byte offsets of the new layout
+	const uint32_t* nfirst;      // n_local + 1: first new record of every local slot, all new records numbered through
+	const uint32_t* tile_slot;   // tiles + 1 (create_tile_slots_kernel)
+	const uint64_t* slot_ids;
+	const CRecipe* recipe;       // K entries
+	size_t Nd;                   // doubles to write: new records * K
+	uint32_t K, k0, k1;
+};
+
+// err[0]: the lowest local slot whose count is refused (~0: none); err[1]: a
+// local cell's bytes are no whole records
+__global__ void create_counts_kernel(const uint64_t* __restrict__ voff, const uint64_t* __restrict__ slot_ids,
+                                     size_t n_slots, size_t n_local, uint64_t rec, const double* __restrict__ F,
+                                     double count, int round_random, uint32_t k0, uint32_t k1,
+                                     uint64_t* __restrict__ sizes, uint32_t* __restrict__ err) {
+	for (size_t s = blockIdx.x * size_t(blockDim.x) + threadIdx.x; s <= n_slots; s += size_t(gridDim.x) * blockDim.x) {
+		if (s == n_slots) {
+			sizes[s] = 0;
+			continue;
+		}
+		const uint64_t old = voff[s + 1] - voff[s];
+		uint64_t add = 0;
+		if (s < n_local) {
+			if ((old / rec) * rec != old) err[1] = 1;
+			double v = F ? count * F[s] : count;
+			if (!(v >= 0.0) || v >= 2147483648.0) {
+				atomicMin(&err[0], uint32_t(s));
+			} else {
+				if (round_random) {
+					const uint64_t id = slot_ids[s];
+					uint32_t w[4];
+					philox4x32_10(uint32_t(id), uint32_t(id >> 32), 0xFFFFFFFFu, 0xFFFFFFFFu, k0, k1, w);
+					const double u = philox_uniform(w[0], w[1]);
+					v = v + u;
+				}
+				add = uint64_t(floor(v)) * rec;
+			}
+		}
+		sizes[s] = old + add;
+	}
+}
+
+// the new records in front of every slot: the bytes the new layout put before
+// it less the bytes the old one did
+__global__ void create_first_kernel(const uint64_t* __restrict__ noff, const uint64_t* __restrict__ ooff, size_t n,
+                                    uint64_t rec, uint32_t* __restrict__ nfirst) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x)
+		nfirst[i] = uint32_t((noff[i] - ooff[i]) / rec);
+}
+
+// slot of the first double's record of every block pass (and, last entry, of the last record)
+__global__ void create_tile_slots_kernel(const uint32_t* __restrict__ nfirst, size_t n_local, size_t N, uint32_t K,
+                                         size_t tiles, uint32_t* __restrict__ tile_slot) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i <= tiles; i += size_t(gridDim.x) * blockDim.x) {
+		const size_t p = i < tiles ? (i * kCB) / K : N - 1;
+		tile_slot[i] = uint32_t(upper_bound_idx<uint32_t>(nfirst, 0, n_local + 1, uint32_t(p)) - 1);
+	}
+}
+
+// the next double towards -inf of a finite value
+__device__ __forceinline__ double pred(double h) {
+	long long b = __double_as_longlong(h);
+	if (h > 0.0)
+		b--;
+	else if (h < 0.0)
+		b++;
+	else
+		b = (long long)0x8000000000000001ull;
+	return __longlong_as_double(b);
+}
+
+// 2^-k, exact
+__device__ __forceinline__ double pow2_neg(int k) { return __longlong_as_double((1023ll - k) << 52); }
+
+// center and length of dimension d of the cell id: geometry_fill_kernel's
+// expressions.  Its quotients have powers of two as divisors; they are the
+// products with the exact reciprocals here, the same bits (cell_box)
+__device__ __forceinline__ void create_center_length(const MapCtx& m, const CGeo& G, uint64_t id, uint32_t d,
+                                                     double& center, double& L) {
+	uint64_t i0 = 0, i1 = 0, i2 = 0;
+	const int lvl = map_indices(m, id, i0, i1, i2);
+	const uint64_t ind = d == 0 ? i0 : d == 1 ? i1 : i2;
+	const double inv_lvl = pow2_neg(lvl < 0 ? 0 : lvl), inv_fine = pow2_neg(m.R);
+	if (G.c) {
+		const uint32_t off = d == 0 ? G.off[0] : d == 1 ? G.off[1] : G.off[2];
+		const uint64_t c_i = ind >> m.R;
+		const double c0 = G.c[off + c_i];
+		const double extent = G.c[off + c_i + 1] - c0;
+		L = extent * inv_lvl;
+		const double length_of_index = extent * inv_fine;
+		const double in_cell = length_of_index * double(ind - (c_i << m.R));
+		const double low = c0 + in_cell;
+		center = low + L / 2;
+	} else {
+		const double start = d == 0 ? G.start[0] : d == 1 ? G.start[1] : G.start[2];
+		const double l0 = d == 0 ? G.l0[0] : d == 1 ? G.l0[1] : G.l0[2];
+		L = l0 * inv_lvl;
+		const double along = double(ind) * l0;
+		const double rel = along * inv_fine;
+		const double low = start + rel;
+		center = low + L / 2;
+	}
+}
+
+// Every double is A + B * z, one product and one sum: a position with
+// A = center, B = L, z = u - 0.5 (then clamped), a recipe's with A = base,
+// B = spread, z = the uniform or the normal.  The lanes of a wave hold
+// different doubles of a record, so the kernel keeps what they share in one
+// path - one Philox block for every lane that needs one, one product and sum
+// - and branches only for the geometry and for the normal's log, sqrt and cos.
+__global__ __launch_bounds__(kCB) void particles_create_kernel(const MapCtx m, const CGeo G, const CArgs a) {
+	__shared__ uint32_t s_off[kOffCache];
+	const size_t tiles = (a.Nd + kCB - 1) / kCB;
+	for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+		const size_t d0 = t * kCB;
+		const size_t r0 = d0 / a.K;  // the same in every lane
+		const uint32_t j0 = uint32_t(d0 - r0 * a.K);
+		__syncthreads();
+		// the slots of the pass's first and last record bound every search
+		const size_t lo = a.tile_slot[t], hi = a.tile_slot[t + 1];
+		const size_t span = hi - lo + 2;  // offsets lo .. hi + 1
+		const bool cached = span <= size_t(kOffCache);
+		if (cached)
+			for (size_t i = threadIdx.x; i < span; i += kCB) s_off[i] = a.nfirst[lo + i];
+		__syncthreads();
+		if (d0 + threadIdx.x >= a.Nd) continue;
+		const uint32_t within = j0 + threadIdx.x;
+		const uint32_t dr = within / a.K;
+		const uint32_t j = within - dr * a.K;
+		const uint32_t r = uint32_t(r0) + dr;
+		const size_t c = cached ? lo + upper_bound_idx<uint32_t>(s_off, 0, span, r) - 1
+		                        : upper_bound_idx<uint32_t>(a.nfirst, lo, hi + 2, r) - 1;
+		const uint32_t f0 = cached ? s_off[c - lo] : a.nfirst[c];
+		const uint32_t f1 = cached ? s_off[c - lo + 1] : a.nfirst[c + 1];
+		const uint32_t i = r - f0;
+		// the cell's new records end where its bytes end
+		double* dst = a.pool + (a.noff[c + 1] / 8 - size_t(f1 - f0) * a.K) + size_t(i) * a.K + j;
+		const uint64_t id = a.slot_ids[c];
+		const bool pos = j < 3;
+		int kind = 1;
+		double A, B = 0.0;
+		if (pos) {
+			create_center_length(m, G, id, j, A, B);
+		} else {
+			const CRecipe R = a.recipe[j];
+			kind = R.kind;
+			A = R.fa ? R.a * R.fa[c] : R.a;
+			if (kind != 0) B = R.fb ? R.b * R.fb[c] : R.b;
+		}
+		double val = A;  // a constant
+		if (kind != 0) {
+			uint32_t w[4];
+			philox4x32_10(uint32_t(id), uint32_t(id >> 32), i, pos ? (j < 2 ? 0u : 1u) : j, a.k0, a.k1, w);
+			const double first = philox_uniform(w[0], w[1]), second = philox_uniform(w[2], w[3]);
+			double z;
+			if (pos) {
+				const double u = j == 1 ? second : first;
+				z = u - 0.5;
+			} else if (kind == 2) {
+				const double q = 1.0 - first;
+				const double lg = log(q);
+				const double tt = -2.0 * lg;
+				const double rad = sqrt(tt);
+				const double theta = 6.283185307179586 * second;
+				const double cs = cos(theta);
+				z = rad * cs;
+			} else {
+				z = first;
+			}
+			const double bz = B * z;
+			val = A + bz;
+			if (pos) {
+				const double half = B / 2;
+				const double low = A - half;
+				const double high = A + half;
+				val = fmin(fmax(val, low), pred(high));
+			}
+		}
+		*dst = val;
+	}
+}
+
+}  // namespace
+
+void particles_create(Grid& g, int fid, int K, int count_field, double count, int round_random, const int* recipe_i,
+                      const double* recipe_d, uint64_t seed, uint64_t* created) {
+	DX_REQUIRE(created, "null pointer");
+	*created = 0;
+	Field& f = field(g, fid);
+	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	DX_REQUIRE(K >= 3, "a particle record has at least 3 doubles (the position)");
+	DX_REQUIRE(round_random == 0 || round_random == 1, "round_random must be 0 (floor) or 1 (random rounding)");
+	DX_REQUIRE(std::isfinite(count), "count must be finite");
+	DX_REQUIRE(K == 3 || (recipe_i && recipe_d), "null pointer");
+	const double* F = nullptr;
+	if (count_field != -1) F = reinterpret_cast<const double*>(fp64_cell_field(g, count_field, "count_field").data.p);
+	std::vector<CRecipe> rc(static_cast<size_t>(K));
+	for (int j = 0; j < K; j++) {
+		CRecipe& R = rc[size_t(j)];
+		R = CRecipe{nullptr, nullptr, 0.0, 0.0, 0};
+		if (j < 3) continue;  // the position: its entries are ignored
+		R.kind = recipe_i[3 * j];
+		DX_REQUIRE(R.kind >= 0 && R.kind <= 2,
+		           "recipe kind of double " + std::to_string(j) + " must be 0 (constant), 1 (uniform) or 2 (normal)");
+		const int bf = recipe_i[3 * j + 1], sf = recipe_i[3 * j + 2];
+		if (bf != -1) R.fa = reinterpret_cast<const double*>(fp64_cell_field(g, bf, "a recipe's base_field").data.p);
+		if (sf != -1) R.fb = reinterpret_cast<const double*>(fp64_cell_field(g, sf, "a recipe's spread_field").data.p);
+		R.a = recipe_d[2 * j];
+		R.b = recipe_d[2 * j + 1];
+	}
+	require_geometry(g);
+	hipStream_t s = g.s_comp;
+	const size_t ns = g.n_slots, nl = g.n_local;
+	if (!ns || !nl) return;
+	if (!f.voff.p) var_reset(f, ns, s);
+	const uint64_t rec = uint64_t(K) * sizeof(double);
+	const uint32_t k0 = uint32_t(seed), k1 = uint32_t(seed >> 32);
+
+	// 1. the new sizes and the refusals
+	DBuf<uint64_t> sizes, noff;
+	DBuf<uint32_t> err;
+	sizes.alloc(ns + 1);
+	noff.alloc(ns + 1);
+	err.alloc(2);
+	const uint32_t err0[2] = {0xFFFFFFFFu, 0u};
+	h2d(err.p, err0, sizeof(err0), s);
+	create_counts_kernel<<<grid_for(ns + 1, 256), 256, 0, s>>>(f.voff.p, g.slot_ids.p, ns, nl, rec, F, count, round_random,
+	                                                         k0, k1, sizes.p, err.p);
+	HIP_CHECK(hipGetLastError());
+	uint32_t herr[2] = {0, 0};
+	d2h_small(herr, err.p, sizeof(herr), s);
+	DX_REQUIRE(!herr[1], "a cell's payload is not a multiple of 8 * record_doubles bytes");
+	if (herr[0] != 0xFFFFFFFFu) {
+		uint64_t id = 0;
+		d2h_small(&id, g.slot_ids.p + herr[0], sizeof(id), s);
+		DX_REQUIRE(false, "the count of cell " + std::to_string(id) + " is NaN, negative or at least 2^31");
+	}
+
+	// 2. the new layout, the old records in front
+	const uint64_t old_total = var_total(f, ns, s);
+	const uint64_t total = scan_exclusive_u64(sizes.p, noff.p, ns, s);
+	const uint64_t N = (total - old_total) / rec;
+	if (!N) return;
+	DX_REQUIRE(total / rec < (uint64_t(1) << 31), "more than 2^31 particles on one process");
+	var_relay(f, ns, noff, total, false, s);  // noff: the previous offsets from here on
+
+	// 3. generate
+	DBuf<uint32_t> nfirst, tile_slot;
+	DBuf<CRecipe> drc;
+	nfirst.alloc(nl + 1);
+	create_first_kernel<<<grid_for(nl + 1, 256), 256, 0, s>>>(f.voff.p, noff.p, nl + 1, rec, nfirst.p);
+	HIP_CHECK(hipGetLastError());
+	const size_t Nd = size_t(N) * size_t(K);
+	const size_t tiles = (Nd + kCB - 1) / kCB;
+	tile_slot.alloc(tiles + 1);
+	create_tile_slots_kernel<<<grid_for(tiles + 1, 256), 256, 0, s>>>(nfirst.p, nl, size_t(N), uint32_t(K), tiles,
+	                                                                tile_slot.p);
+	HIP_CHECK(hipGetLastError());
+	drc.alloc(size_t(K));
+	h2d(drc.p, rc.data(), size_t(K) * sizeof(CRecipe), s);
+	CGeo G{};
+	if (g.str.active) {
+		const StretchedView V = stretched_view(g);
+		G.c = V.c;
+		for (int d = 0; d < 3; d++) G.off[d] = V.off[d];
+	} else {
+		for (int d = 0; d < 3; d++) {
+			G.start[d] = g.start[d];
+			G.l0[d] = g.l0[d];
+		}
+	}
+	CArgs a{};
+	a.pool = reinterpret_cast<double*>(f.data.p);
+	a.noff = f.voff.p;
+	a.nfirst = nfirst.p;
+	a.tile_slot = tile_slot.p;
+	a.slot_ids = g.slot_ids.p;
+	a.recipe = drc.p;
+	a.Nd = Nd;
+	a.K = uint32_t(K);
+	a.k0 = k0;
+	a.k1 = k1;
+	k_time_begin(g);
+	particles_create_kernel<<<grid_for(tiles, 1, 1u << 16), kCB, 0, s>>>(g.m, G, a);
+	HIP_CHECK(hipGetLastError());
+	k_time_end(g);
+	field_written(f);
+	HIP_CHECK(hipStreamSynchronize(s));  // the offsets and the recipe go out of scope
+	*created = N;
 }
 
 }  // namespace dccrgx

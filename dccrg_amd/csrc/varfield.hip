@@ -141,13 +141,10 @@ void var_sizes(const Field& f, const int32_t* slots, size_t slot0, size_t n, uin
 	HIP_CHECK(hipGetLastError());
 }
 
-void var_resize(Field& f, size_t n_slots, const uint64_t* new_sizes, hipStream_t s) {
-	DBuf<uint64_t> noff;
-	noff.alloc(n_slots + 1);
-	const uint64_t total = scan_exclusive_u64(new_sizes, noff.p, n_slots, s);
+void var_relay(Field& f, size_t n_slots, DBuf<uint64_t>& noff, uint64_t total, bool zero, hipStream_t s) {
 	DBuf<uint8_t> nd;
 	nd.alloc(total + 1);
-	HIP_CHECK(hipMemsetAsync(nd.p, 0, total + 1, s));
+	if (zero) HIP_CHECK(hipMemsetAsync(nd.p, 0, total + 1, s));
 	if (n_slots && f.data.p) {
 		var_resize_copy_kernel<<<wave_grid(n_slots), 256, 0, s>>>(f.data.p, f.voff.p, nd.p, noff.p, n_slots);
 		HIP_CHECK(hipGetLastError());
@@ -155,6 +152,13 @@ void var_resize(Field& f, size_t n_slots, const uint64_t* new_sizes, hipStream_t
 	HIP_CHECK(hipStreamSynchronize(s));
 	f.data.swap(nd);
 	f.voff.swap(noff);
+}
+
+void var_resize(Field& f, size_t n_slots, const uint64_t* new_sizes, hipStream_t s) {
+	DBuf<uint64_t> noff;
+	noff.alloc(n_slots + 1);
+	const uint64_t total = scan_exclusive_u64(new_sizes, noff.p, n_slots, s);
+	var_relay(f, n_slots, noff, total, true, s);
 }
 
 size_t var_gather(const Field& f, const int32_t* slots, size_t n, DBuf<uint64_t>& sizes, DBuf<uint8_t>& bytes,

@@ -1021,6 +1021,55 @@ class Dccrg:
         check(lib().dccrgx_particles_boris(self.h, field.id, int(record_doubles), int(e_first), int(b_first), w,
                                            float(factor)))
 
+    CREATE_KIND = {"const": 0, "uniform": 1, "normal": 2}
+
+    def particles_create(self, field, record_doubles, count=1.0, count_field=None, round="floor", recipe=None,
+                         seed=0):
+        """Appends new records to the local cells' lists of the variable
+        float64 field `field`, on the device; returns how many this process
+        created.  A cell c receives floor(v) of them (round="floor") or
+        floor(v + u) with a uniform u of its own (round="random"), v = count
+        or count * count_field[c].  Doubles 0..2 are a uniform position inside
+        the cell; `recipe` maps a double j >= 3 to ("const", a),
+        ("uniform", a, b) or ("normal", a, b), optionally followed by a dict
+        {"base_field": Fa, "spread_field": Fb} of float64 Fields: the value is
+        base, base + spread * u or base + spread * z with base = a (* Fa[c]),
+        spread = b (* Fb[c]), u uniform in [0, 1), z standard normal.  Doubles
+        not named are constant 0.  Every value is a function of (seed, cell
+        id, index among the cell's new records, double) alone, so the records
+        do not depend on the processes, the slots or what the lists hold.
+        include/dccrgx.h states the operations."""
+        K = int(record_doubles)
+        if round not in ("floor", "random"):
+            raise ValueError(f"round must be 'floor' or 'random', not {round!r}")
+        ri = [0, -1, -1] * max(K, 0)
+        rd = [0.0, 0.0] * max(K, 0)
+        for j, spec in (recipe or {}).items():
+            j = int(j)
+            if not 3 <= j < K:
+                raise ValueError(f"recipe names double {j}: outside 3 .. record_doubles - 1")
+            spec = tuple(spec)
+            opts = {}
+            if spec and isinstance(spec[-1], dict):
+                opts, spec = spec[-1], spec[:-1]
+            if set(opts) - {"base_field", "spread_field"}:
+                raise ValueError(f"unknown recipe options {sorted(opts)}")
+            kind = spec[0]
+            if len(spec) != (2 if kind in ("const", 0) else 3):
+                raise ValueError('a recipe entry is ("const", a), ("uniform", a, b) or ("normal", a, b)')
+            ri[3 * j] = self.CREATE_KIND[kind] if isinstance(kind, str) else int(kind)
+            for k, name in ((1, "base_field"), (2, "spread_field")):
+                fl = opts.get(name)
+                ri[3 * j + k] = -1 if fl is None else fl.id
+            rd[2 * j] = float(spec[1])
+            rd[2 * j + 1] = float(spec[2]) if len(spec) > 2 else 0.0
+        made = C.c_uint64(0)
+        check(lib().dccrgx_particles_create(self.h, field.id, K, -1 if count_field is None else count_field.id,
+                                            float(count), int(round == "random"),
+                                            (C.c_int * max(len(ri), 1))(*ri), (C.c_double * max(len(rd), 1))(*rd),
+                                            int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(made)))
+        return int(made.value)
+
     def gradient(self, field, out, scale=1.0, region="all", halo=False):
         """out[d] = scale * the d-component of the cell-centred gradient of the
         float64 field `field` in every local cell of `region`; `out` is three

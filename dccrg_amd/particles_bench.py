@@ -207,10 +207,16 @@ def main(argv=None):
                    help="with --stretched: files of lines the parent commit's particles_bench printed in the same "
                         "machine visit (comma-separated), recorded as the parent's Cartesian step; with --adapt: "
                         "files of measure_adapt(follow=False) results taken with the parent commit's library")
+    p.add_argument("--create", action="store_true",
+                   help="Dccrg.particles_create into an empty pool and as an append of one record per cell to the full "
+                        "pool (K = 10), beside the host way (NumPy generation and upload) and one re-lay of the pool, "
+                        "alternating in one run; writes profiles/particles_bench_create.json unless --out")
     a = p.parse_args(argv)
 
     import torch  # noqa: F401  (one HIP runtime for the process)
 
+    if a.create:
+        return main_create(a)
     if a.reduce:
         return main_reduce(a)
     if a.curl:
@@ -1172,6 +1178,125 @@ def main_reduce(a):
     print(txt, flush=True)
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                 "particles_bench_reduce.json")
+    with open(out, "w") as f:
+        f.write(txt + "\n")
+
+
+def main_create(a):
+    """particles_create on the benchmark's own pool (base^3 cells, ppc records
+    of K = 10): (a) into an empty pool, (b) one more record per cell behind the
+    full pool, (c) the host way (NumPy generation of the same content, resize
+    and one flat upload), (d) one re-lay of the full pool; --repeats rounds of
+    a, b, d in turn on one grid, c twice at most."""
+    import dccrg_amd
+    from dccrg_amd._lib import check, lib
+
+    Kb, n = PIC_K, a.base
+    g = dccrg_amd.Dccrg(0, 1, 0).set_initial_length((n, n, n)).set_neighborhood_length(1)
+    g.set_maximum_refinement_level(0).set_periodic(True, True, True).initialize()
+    fld = g.add_variable_field("particles", np.float64, True)
+    ids = g.slot_ids()[: g.n_local]
+    nc = int(ids.size)
+    k = (ids - np.uint64(1)).astype(np.int64)
+    ix = np.stack([k % n, (k // n) % n, k // (n * n)], axis=1).astype(np.float64)
+    dens = g.add_field("density", np.float64, False)
+    dens.set(1 + 0.1 * np.cos(2 * np.pi * (ix[:, 0] + 0.5) / n))
+    recipe = {3: ("normal", 0.0, 0.1), 4: ("normal", 0.0, 0.1), 5: ("normal", 0.0, 0.1),
+              PIC_Q: ("const", 1.0, dict(base_field=dens))}
+    N = nc * a.ppc
+    full = np.full(nc, a.ppc * Kb, np.uint64)
+    empty = np.zeros(nc, np.uint64)
+
+    def timed(call):
+        g.synchronize()
+        g.kernel_timing(1)
+        t0 = time.perf_counter()
+        r = call()
+        g.synchronize()
+        dt = (time.perf_counter() - t0) * 1e3
+        kms, kn = g.kernel_timing(0)
+        return dt, (kms if kn else None), r
+
+    def host_way():
+        tg = time.perf_counter()
+        rng = np.random.default_rng(1)
+        rec = np.zeros((nc, a.ppc, Kb))
+        rec[:, :, 0:3] = ix[:, None, :] + rng.random((nc, a.ppc, 3))
+        rec[:, :, 3:6] = 0.1 * rng.standard_normal((nc, a.ppc, 3))
+        rec[:, :, PIC_Q] = (1 + 0.1 * np.cos(2 * np.pi * (ix[:, 0] + 0.5) / n))[:, None]
+        gen_ms.append((time.perf_counter() - tg) * 1e3)
+        rec = rec.reshape(-1)
+        fld.resize(full)
+        check(lib().dccrgx_variable_field_upload(g.h, fld.id, 0, nc, rec.ctypes.data_as(C.c_void_p), rec.nbytes))
+
+    # where the generate kernel's time goes: the same call with the three velocity doubles constant (positions
+    # alone compute Philox blocks) and uniform (no log, sqrt, cos)
+    by_content = {"velocities_constant": {PIC_Q: recipe[PIC_Q]},
+                  "velocities_uniform": {**recipe, **{j: ("uniform", -0.1, 0.2) for j in (3, 4, 5)}}}
+    runs = {k: dict(host_ms=[], kernel_ms=[]) for k in ("create_empty", "append_one", "host_way", "relay",
+                                                         *by_content)}
+    gen_ms = []
+    for rnd in range(1 + max(a.repeats, 1)):  # the first round warms up
+        fld.resize(empty)
+        ta = timed(lambda: g.particles_create(fld, Kb, count=a.ppc, recipe=recipe, seed=rnd))
+        assert ta[2] == N and int(fld.sizes(0, 4).sum()) == 4 * a.ppc * Kb * 8
+        tb = timed(lambda: g.particles_create(fld, Kb, count=1.0, recipe=recipe, seed=1000 + rnd))
+        assert tb[2] == nc
+        fld.resize(full)
+        td = timed(lambda: fld.resize(full))
+        todo = [("create_empty", ta), ("append_one", tb), ("relay", td)]
+        for name, rc in by_content.items():
+            fld.resize(empty)
+            todo.append((name, timed(lambda: g.particles_create(fld, Kb, count=a.ppc, recipe=rc, seed=rnd))))
+        if rnd <= 2:
+            fld.resize(empty)
+            todo.append(("host_way", timed(host_way)))
+        if rnd == 0:
+            continue
+        for name, (dt, kms, _) in todo:
+            runs[name]["host_ms"].append(dt)
+            if kms is not None:
+                runs[name]["kernel_ms"].append(kms)
+    # what was created: every record inside its cell, the weight the density's
+    fld.resize(empty)
+    g.particles_create(fld, Kb, count=a.ppc, recipe=recipe, seed=5)
+    got = g.particles_reduce(fld, [("sum", None, None), ("sum", PIC_Q, None), ("sum", 3, None), ("sum", 3, 3)], Kb)
+    st = g.particles_step(fld, Kb, (0.0, 0.0, 0.0), 0.0)
+    assert got[0] == N and st["stayed"] == N and st["lost"] == 0, (got, st)
+    g.close()
+    res = {}
+    for name, r in runs.items():
+        res[name] = dict(host_ms=float(np.median(r["host_ms"])), host_runs_ms=r["host_ms"])
+        if r["kernel_ms"]:
+            res[name].update(kernel_ms=float(np.median(r["kernel_ms"])), kernel_runs_ms=r["kernel_ms"])
+    res["host_way"]["numpy_generation_ms"] = float(np.median(gen_ms[1:] or gen_ms))
+    rec_bytes = Kb * 8
+    ce = res["create_empty"]
+    ce["bytes_written"] = N * rec_bytes
+    ce["frac_of_peak_whole_call"] = N * rec_bytes / (ce["host_ms"] / 1e3) / 1e9 / PEAK_HBM_GBS
+    if "kernel_ms" in ce:
+        ce["frac_of_peak_generate_kernel"] = N * rec_bytes / (ce["kernel_ms"] / 1e3) / 1e9 / PEAK_HBM_GBS
+    line = {"metric": "particles_create", "value": N / (ce["host_ms"] / 1e3), "unit": "records/s", "n_gpus": 1,
+            "steps": a.repeats, "warmup": 1, "higher_is_better": True, "dtype": "fp64",
+            "config": {"workload": f"{n}^3 periodic cells, {a.ppc} records of K = {Kb} per cell: uniform positions, three "
+                                   "normal velocity components, a weight scaled by a density field, three zero doubles "
+                                   "(six of ten doubles compute a Philox block, three of them a normal); host_ms: the "
+                                   "synchronized host clock around the whole call (its checks, the scan, the fresh pool "
+                                   "and the re-lay included); kernel_ms: between device events around the generate kernel "
+                                   "alone; host_way: NumPy generation of the same content, resize and one flat upload "
+                                   "(the benchmark's own loader, quicker than VariableField.set's list of arrays); relay: "
+                                   "VariableField.resize of the full pool, sizes unchanged",
+                       "cells": nc, "records": N, "record_bytes": rec_bytes},
+            "create_empty": ce, "append_one": res["append_one"], "host_way": res["host_way"], "relay": res["relay"],
+            "create_empty_by_content": {k: res[k] for k in by_content},
+            "create_over_host_way": ce["host_ms"] / res["host_way"]["host_ms"],
+            "append_over_relay": res["append_one"]["host_ms"] / res["relay"]["host_ms"],
+            "created_mean_v": got[2] / N, "created_var_v_over_thermal2": (got[3] / N - (got[2] / N) ** 2) / 0.01,
+            "created_charge": got[1]}
+    txt = json.dumps(line)
+    print(txt, flush=True)
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "particles_bench_create.json")
     with open(out, "w") as f:
         f.write(txt + "\n")
 

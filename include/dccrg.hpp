@@ -1219,6 +1219,49 @@ public:
 		                                    st.data()));
 		return st;
 	}
+	// one double (j >= 3) of the records particles_create makes: base + spread
+	// * r with base = a (times base_field[c]), spread = b (times
+	// spread_field[c]) and r nothing (CONSTANT), a uniform in [0, 1) or a
+	// standard normal
+	struct Create_Spec {
+		enum Kind { CONSTANT = 0, UNIFORM = 1, NORMAL = 2 };
+		int record_double;
+		Kind kind;
+		double a, b;
+		const Device_Field<double>* base_field;
+		const Device_Field<double>* spread_field;
+	};
+	// new records appended to the local cells' lists on the device: cell c
+	// receives floor(v) of them, or floor(v + u) with a uniform u of its own
+	// (round_random), v = count or count * count_field[c]; doubles 0..2 a
+	// uniform position inside the cell, the doubles the recipe names by their
+	// Create_Spec, the others 0.  Every value is a function of (seed, cell id,
+	// index among the cell's new records, double): the records do not depend
+	// on the processes, the slots or what the lists hold (dccrgx.h has the
+	// operations).  Returns the number this process created.
+	uint64_t particles_create(const Device_Variable_Field<double>& particles, const int record_doubles,
+	                          const double count, const Device_Field<double>* count_field = nullptr,
+	                          const bool round_random = false, const std::vector<Create_Spec>& recipe = {},
+	                          const uint64_t seed = 0) {
+		const size_t K = record_doubles > 0 ? size_t(record_doubles) : 0;
+		std::vector<int> ri(3 * K + 1, -1);
+		std::vector<double> rd(2 * K + 1, 0.0);
+		for (size_t j = 0; j < K; j++) ri[3 * j] = 0;
+		for (const auto& s : recipe) {
+			if (s.record_double < 3 || size_t(s.record_double) >= K)
+				throw std::invalid_argument("particles_create: a recipe names a double outside 3 .. record_doubles - 1");
+			const size_t j = size_t(s.record_double);
+			ri[3 * j] = int(s.kind);
+			ri[3 * j + 1] = s.base_field ? s.base_field->id() : -1;
+			ri[3 * j + 2] = s.spread_field ? s.spread_field->id() : -1;
+			rd[2 * j] = s.a;
+			rd[2 * j + 1] = s.b;
+		}
+		uint64_t created = 0;
+		detail::check(dccrgx_particles_create(g_, particles.id(), record_doubles, count_field ? count_field->id() : -1,
+		                                      count, round_random ? 1 : 0, ri.data(), rd.data(), seed, &created));
+		return created;
+	}
 	// particles -> a cell field: out[c] = the sum of q W(p, c) over the records
 	// of the local cell c and of the distinct leaves of its neighbors_of
 	// (copies of remote neighbors included: update them first); q = double

@@ -565,6 +565,63 @@ int dccrgx_particles_deposit_moments(dccrgx_grid* g, int var_field, int record_d
  * weight_double is -1 or in [6, K) outside both. */
 int dccrgx_particles_boris(dccrgx_grid* g, int var_field, int record_doubles, int e_first, int b_first,
                            int weight_double, double factor);
+/* create: new records are appended to the lists of the local cells, on the
+ * device.  Every value is a function of (seed, cell id, index i among the
+ * cell's new records, double j) alone: not of the slot, the number of
+ * processes, what the lists hold or the launch; two calls give equal bits.
+ *
+ * Random numbers: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, key
+ * increments 0x9E3779B9, 0xBB67AE85), key = (seed's low word, seed's high
+ * word), counter = (id's low word, id's high word, i, block number).  A
+ * block's words w0..w3 give two uniforms in [0, 1):
+ * first = double((uint64(w0) << 21) | (w1 >> 11)) * 2^-53, second the same
+ * from w2, w3.  (Known answer: counter 0,0,0,0 under key 0,0 gives
+ * 6627e8d5 e169c58d bc57ac4c 9b00dbd8.)
+ *
+ * Counts, for every local cell c: v = count with count_field == -1, else
+ * v = count * F[c] (one product; F a fixed fp64 field); round_random == 0:
+ * n_c = floor(v); round_random == 1: n_c = floor(v + u), one rounded sum, u
+ * the first uniform of the block with counter (id low, id high, 0xFFFFFFFF,
+ * 0xFFFFFFFF).  A v that is NaN, negative or >= 2^31 in any local cell is
+ * DCCRGX_EINVAL, found on the device with nothing changed; dccrgx_last_error
+ * names the cell.
+ *
+ * Placement: a cell's existing records keep their bits and their order, the
+ * n_c new ones follow, i = 0 .. n_c - 1.  Remote copies receive nothing and
+ * keep their bytes.  *created = the process's total; a total of 0 changes
+ * nothing (no write is recorded).
+ *
+ * Doubles 0..2, the position (their recipe entries are ignored): with center
+ * and L what dccrgx_geometry_fill writes for the cell (Cartesian or
+ * stretched), u_x, u_y = first, second of block 0, u_z = first of block 1:
+ *   h = u - 0.5 (exact);  x = center + h * L (one product, one sum)
+ *   lo = center - L / 2;  hi = center + L / 2
+ *   stored: min(max(x, lo), pred(hi)), pred the next double towards -inf,
+ * so the position is in [lo, hi) whatever the rounding.
+ *
+ * Double j >= 3, recipe_i[3 j ..] = (kind, base_field, spread_field),
+ * recipe_d[2 j ..] = (a, b), block j:  base = a with base_field == -1, else
+ * a * Fa[c];  spread = b with spread_field == -1, else b * Fb[c] (one product
+ * each; fixed fp64 fields).
+ *   kind 0 (constant): base; no block is computed, spread is not formed
+ *   kind 1 (uniform):  base + spread * first
+ *   kind 2 (normal):   base + spread * z with
+ *       w = 1.0 - first (exact, in (0, 1]);  t = -2.0 * log(w);  r = sqrt(t)
+ *       theta = 6.283185307179586 * second;  z = r * cos(theta)
+ * each one operation, the product rounded before the sum; log and cos are the
+ * device library's, sqrt is correctly rounded.  A weight a * density[c], a
+ * drift Fa[c] (a = 1) and a thermal speed b * Fb[c] are all of this form.
+ * A cell field whose device pointer was handed out is read as it is.
+ *
+ * DCCRGX_EINVAL: a fixed-size var_field; K < 3; a local cell whose bytes are
+ * no multiple of 8 K; a kind outside 0..2 for j >= 3; a field id (count_field,
+ * or a base_field / spread_field of j >= 3) that is neither -1 nor a fixed
+ * 8-byte field; round_random not 0 or 1; count not finite; more than 2^31 - 1
+ * records on the process afterwards; a stretched geometry block without
+ * coordinates (as for per_volume). */
+int dccrgx_particles_create(dccrgx_grid* g, int var_field, int record_doubles /* K */, int count_field, double count,
+                            int round_random, const int* recipe_i /* 3 K: kind, base_field, spread_field */,
+                            const double* recipe_d /* 2 K: a, b */, uint64_t seed, uint64_t* created);
 /* The cell-centred gradient of the fixed fp64 field in_field over the leaves:
  * out_fields[d] (fixed fp64 fields, -1: component not wanted) of every local
  * cell of `region` (DCCRGX_REGION_*; inner then outer writes the bits of all)
