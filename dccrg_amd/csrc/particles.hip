@@ -30,6 +30,8 @@
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
+#include <initializer_list>
+#include <string>
 #include <type_traits>
 
 #include "dccrgx_grid.hpp"
@@ -189,30 +191,43 @@ __device__ __forceinline__ uint64_t stretched_cell_at(const MapCtx& m, const Dev
 	return error_cell;
 }
 
-// a block's copy of the coordinates (the caller syncs); false: they do not fit
-__device__ __forceinline__ bool stage_coordinates(const SGeo& S, double* s_c) {
-	if (S.total > kCoordCache) return false;
-	for (uint32_t i = threadIdx.x; i < S.total; i += blockDim.x) s_c[i] = S.c[i];
-	return true;
-}
-
-__global__ __launch_bounds__(256) void stretched_cells_at_kernel(const MapCtx m, const DevMesh M, const SGeo S,
-                                                                    const double* __restrict__ xyz, size_t n,
-                                                                    uint64_t* __restrict__ ids) {
-	__shared__ double s_c[kCoordCache];
-	const bool cached = stage_coordinates(S, s_c);
-	__syncthreads();
-	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
-		const double x[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-		ids[i] = cached ? stretched_cell_at(m, M, S, s_c, x) : stretched_cell_at(m, M, S, S.c, x);
+// The point location of a kernel, Geo: PGeo (Cartesian) or SGeo (stretched).
+// stage_geometry is the kernel's preamble: a block's copy of a stretched
+// geometry's coordinates in LDS (the caller syncs before the first cell_at);
+// false: they do not fit, or the geometry has none.  cell_at is the smallest
+// known leaf at x under either geometry.
+template <class Geo>
+__device__ __forceinline__ bool stage_geometry(const Geo& G, const double*& s_c) {
+	s_c = nullptr;
+	if constexpr (std::is_same<Geo, SGeo>::value) {
+		__shared__ double s_coords[kCoordCache];
+		s_c = s_coords;
+		if (G.total > kCoordCache) return false;
+		for (uint32_t i = threadIdx.x; i < G.total; i += blockDim.x) s_coords[i] = G.c[i];
+		return true;
 	}
+	return false;
 }
 
-__global__ void cells_at_kernel(const MapCtx m, const DevMesh M, const PGeo G, const double* __restrict__ xyz, size_t n,
+__device__ __forceinline__ uint64_t cell_at(const MapCtx& m, const DevMesh& M, const PGeo& G, const double*, bool,
+                                            const double x[3]) {
+	return existing_cell_at(m, M, G, x);
+}
+
+__device__ __forceinline__ uint64_t cell_at(const MapCtx& m, const DevMesh& M, const SGeo& S, const double* s_c,
+                                            bool cached, const double x[3]) {
+	return cached ? stretched_cell_at(m, M, S, s_c, x) : stretched_cell_at(m, M, S, S.c, x);
+}
+
+template <class Geo>
+__global__ void cells_at_kernel(const MapCtx m, const DevMesh M, const Geo G, const double* __restrict__ xyz, size_t n,
                                 uint64_t* __restrict__ ids) {
+	const double* s_c;
+	const bool cached = stage_geometry(G, s_c);
+	if (s_c) __syncthreads();  // (nothing is staged under PGeo)
 	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
 		const double x[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-		ids[i] = existing_cell_at(m, M, G, x);
+		ids[i] = cell_at(m, M, G, s_c, cached, x);
 	}
 }
 
@@ -242,13 +257,61 @@ __global__ void record_offsets_kernel(const uint64_t* __restrict__ voff, size_t 
 	}
 }
 
-// slot of the first particle of every block pass (and, last entry, of the last particle)
-__global__ void chunk_slots_kernel(const uint32_t* __restrict__ ofirst, size_t n_slots, size_t N, size_t chunks,
-                                   uint32_t* __restrict__ chunk_slot) {
-	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i <= chunks; i += size_t(gridDim.x) * blockDim.x) {
-		const size_t p = i < chunks ? i * kPB : N - 1;
-		chunk_slot[i] = uint32_t(upper_bound_idx<uint32_t>(ofirst, 0, n_slots + 1, uint32_t(p)) - 1);
+// The record search (DESIGN.md "Passes of one step"): the slot of record p is
+// the last one whose offset is <= p.  A side table narrows it per block pass,
+// and the offsets between the pass's first and last slot are searched in LDS
+// when they fit kOffCache, else in global memory.
+//
+// slot of the first record of every block pass (and, last entry, of the last
+// record of all N).  A pass is kPB records, or (kDoubles) kPB doubles of records
+// of K: i * kPB / K records lie before pass i (the step's and the gather's
+// table pays for no division)
+template <bool kDoubles>
+__global__ void pass_slots_kernel(const uint32_t* __restrict__ off, size_t n_slots, size_t N, size_t passes, size_t K,
+                                  uint32_t* __restrict__ pass_slot) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i <= passes; i += size_t(gridDim.x) * blockDim.x) {
+		const size_t p = i == passes ? N - 1 : kDoubles ? (i * kPB) / K : i * kPB;
+		pass_slot[i] = uint32_t(upper_bound_idx<uint32_t>(off, 0, n_slots + 1, uint32_t(p)) - 1);
 	}
+}
+
+// K: 0 for passes of records
+void launch_pass_slots(const uint32_t* off, size_t n_slots, size_t N, size_t passes, size_t K, DBuf<uint32_t>& pass_slot,
+                       hipStream_t s) {
+	pass_slot.alloc(passes + 1);
+	if (K)
+		pass_slots_kernel<true><<<grid_for(passes + 1, 256), 256, 0, s>>>(off, n_slots, N, passes, K, pass_slot.p);
+	else
+		pass_slots_kernel<false><<<grid_for(passes + 1, 256), 256, 0, s>>>(off, n_slots, N, passes, 1, pass_slot.p);
+	HIP_CHECK(hipGetLastError());
+}
+
+// a block pass's window of the offsets, off[lo .. hi + 1]
+struct OffsetWindow {
+	const uint32_t *off, *s_off;  // all offsets; the block's copy of the window (if cached)
+	size_t lo, hi;                // the slots of the pass's first and last record bound every search
+	bool cached;
+
+	__device__ __forceinline__ size_t slot(uint32_t p) const {
+		return cached ? lo + upper_bound_idx<uint32_t>(s_off, 0, hi - lo + 2, p) - 1
+		              : upper_bound_idx<uint32_t>(off, lo, hi + 2, p) - 1;
+	}
+	// off[s] of a slot of the window, read where the search read
+	__device__ __forceinline__ uint32_t at(size_t s) const { return cached ? s_off[s - lo] : off[s]; }
+};
+
+// every thread of a block of kPB calls this once per pass (two barriers: the
+// previous pass's searches end before the copy, the copy before this pass's)
+__device__ __forceinline__ OffsetWindow stage_offsets(const uint32_t* off, const uint32_t* pass_slot, size_t pass,
+                                                      uint32_t* s_off) {
+	__syncthreads();
+	OffsetWindow W{off, s_off, pass_slot[pass], pass_slot[pass + 1], false};
+	const size_t span = W.hi - W.lo + 2;
+	W.cached = span <= size_t(kOffCache);
+	if (W.cached)
+		for (size_t i = threadIdx.x; i < span; i += kPB) s_off[i] = off[W.lo + i];
+	__syncthreads();
+	return W;
 }
 
 // (the mapping, the mesh and the geometry are kernel parameters of their own:
@@ -256,7 +319,7 @@ __global__ void chunk_slots_kernel(const uint32_t* __restrict__ ofirst, size_t n
 struct PArgs {
 	double* pool;
 	const uint32_t* ofirst;      // n_slots + 1 record offsets
-	const uint32_t* chunk_slot;  // chunks + 1 (chunk_slots_kernel)
+	const uint32_t* chunk_slot;  // chunks + 1 (pass_slots_kernel)
 	size_t n_slots, n_local, N;
 	int K;
 	const uint64_t* slot_ids;
@@ -274,38 +337,22 @@ struct PArgs {
 __device__ __forceinline__ const PGeo& wrap_geo(const PGeo& G) { return G; }
 __device__ __forceinline__ const PGeo& wrap_geo(const SGeo& S) { return S.g; }
 
-// Geo: PGeo (Cartesian) or SGeo (stretched: the coordinates staged in LDS
-// once per block when they fit)
 template <class Geo>
 __global__ __launch_bounds__(kPB) void particles_locate_kernel(const MapCtx m, const DevMesh M, const Geo G,
                                                                   const PArgs a) {
-	constexpr bool kStretched = std::is_same<Geo, SGeo>::value;
 	__shared__ uint32_t s_off[kOffCache];
 	__shared__ uint32_t s_cnt[4];
-	double* s_c = nullptr;
-	bool coords_cached = false;
-	if constexpr (kStretched) {
-		__shared__ double s_coords[kCoordCache];
-		s_c = s_coords;
-		coords_cached = stage_coordinates(G, s_c);  // synced by the first pass below
-	}
+	const double* s_c;
+	const bool coords_cached = stage_geometry(G, s_c);  // synced by the first pass below
 	uint32_t n_moved = 0, n_arrived = 0, n_handed = 0, n_lost = 0;
 	if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
 	const size_t chunks = (a.N + kPB - 1) / kPB;
 	for (size_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
 		const size_t p0 = ch * kPB, p1 = p0 + kPB < a.N ? p0 + kPB : a.N;
-		__syncthreads();
-		// the slots of the pass's first and last particle bound every search
-		const size_t lo = a.chunk_slot[ch], hi = a.chunk_slot[ch + 1];
-		const size_t span = hi - lo + 2;  // offsets lo .. hi + 1
-		const bool cached = span <= size_t(kOffCache);
-		if (cached)
-			for (size_t i = threadIdx.x; i < span; i += kPB) s_off[i] = a.ofirst[lo + i];
-		__syncthreads();
+		const OffsetWindow W = stage_offsets(a.ofirst, a.chunk_slot, ch, s_off);
 		const size_t p = p0 + threadIdx.x;
 		if (p >= p1) continue;
-		const size_t s = cached ? lo + upper_bound_idx<uint32_t>(s_off, 0, span, uint32_t(p)) - 1
-		                        : upper_bound_idx<uint32_t>(a.ofirst, lo, hi + 2, uint32_t(p)) - 1;
+		const size_t s = W.slot(uint32_t(p));
 		double* r = a.pool + p * size_t(a.K);
 		double x[3];
 #pragma unroll
@@ -316,11 +363,7 @@ __global__ __launch_bounds__(kPB) void particles_locate_kernel(const MapCtx m, c
 			x[d] = real_coordinate(wrap_geo(G), d, moved);
 			r[d] = x[d];
 		}
-		uint64_t dst;
-		if constexpr (kStretched)
-			dst = coords_cached ? stretched_cell_at(m, M, G, s_c, x) : stretched_cell_at(m, M, G, G.c, x);
-		else
-			dst = existing_cell_at(m, M, G, x);
+		const uint64_t dst = cell_at(m, M, G, s_c, coords_cached, x);
 		const uint64_t own = a.slot_ids[s];
 		const bool local = s < a.n_local;
 		int32_t dest = -1;
@@ -500,6 +543,74 @@ SGeo make_sgeo(Grid& g) {
 	return S;
 }
 
+// What the particle calls share on the host.  A call names its field (the
+// constructor), checks its own arguments, and then prepare()s: the checks on
+// the grid, K, the shape and the geometry, in this order, the record offsets
+// of every slot and the record counts (all zero and no offsets: no pool).
+struct ParticleCall {
+	Grid& g;
+	Field& f;
+	hipStream_t s;
+	int K = 0;
+	size_t N_all = 0;    // records of the pool, the remote copies' included
+	size_t N_local = 0;  // records of the local cells, the pool's first (where asked for)
+	DBuf<uint32_t> ofirst, chunk_slot;
+
+	ParticleCall(Grid& g_, int fid) : g(g_), f(field(g_, fid)), s(g_.s_comp) {
+		DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	}
+
+	double* pool() const { return reinterpret_cast<double*>(f.data.p); }
+
+	// lengths: the call reads cell lengths (CIC does anyway); local: N_local is wanted
+	void prepare(int K_, int shape, bool lengths, bool local) {
+		K = K_;
+		DX_REQUIRE(g.initialized, "not initialized");
+		DX_REQUIRE(K >= 3, "a particle record has at least 3 doubles (the position)");
+		DX_REQUIRE(shape == 0 || shape == 1, "shape must be 0 (NGP) or 1 (CIC)");
+		if (shape == 1) {
+			DX_REQUIRE(g.hood_len >= 1, "CIC needs a neighborhood length of at least 1");
+			DX_REQUIRE(!g.str.active, "CIC needs a Cartesian geometry (a stretched geometry is set)");
+		}
+		if (shape == 1 || lengths) require_geometry(g);
+		const size_t ns = g.n_slots;
+		if (!ns || !f.voff.p) return;
+		const uint64_t rec = uint64_t(K) * sizeof(double);
+		const uint64_t total = var_total(f, ns, s);
+		DX_REQUIRE(total / rec < (uint64_t(1) << 31), "more than 2^31 particles on one process");
+		// record offsets of the slots; every cell a whole number of records
+		DBuf<int32_t> flag;
+		ofirst.alloc(ns + 1);
+		flag.alloc(1);
+		HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, s));
+		record_offsets_kernel<<<grid_for(ns + 1, 256), 256, 0, s>>>(f.voff.p, ns + 1, rec, ofirst.p, flag.p);
+		HIP_CHECK(hipGetLastError());
+		int32_t bad = 0;
+		d2h_small(&bad, flag.p, 4, s);
+		DX_REQUIRE(!bad, "a cell's payload is not a multiple of 8 * record_doubles bytes");
+		N_all = size_t(total / rec);
+		if (local && N_all && g.n_local) N_local = size_t(var_total(f, g.n_local, s) / rec);
+	}
+
+	// the side table of passes of kPB records over the first N (of n_slots slots)
+	void chunk_slots(size_t n_slots, size_t N) {
+		launch_pass_slots(ofirst.p, n_slots, N, (N + kPB - 1) / kPB, 0, chunk_slot, s);
+	}
+
+	// the call's kernels are queued: ofirst and chunk_slot go out of scope
+	void finish() { HIP_CHECK(hipStreamSynchronize(s)); }
+};
+
+// -1 (q = 1), or a double of the record from first_allowed on and outside the
+// three doubles that start at each of `taken`.  (K < 3 is prepare()'s to refuse.)
+void require_weight_double(int K, int wd, int first_allowed, const char* past, std::initializer_list<int> taken = {}) {
+	bool ok = wd >= first_allowed && wd < K;
+	for (int t : taken) ok = ok && !(wd >= t && wd < t + 3);
+	DX_REQUIRE(K < 3 || wd == -1 || ok,
+	           std::string("weight_double must be -1 (q = 1) or a double of the record past the ") + past + " (" +
+	               std::to_string(first_allowed) + " <= weight_double < record_doubles)");
+}
+
 }  // namespace
 
 // the packed device copy of the coordinates, made at first use.  The finest
@@ -554,40 +665,27 @@ void existing_cells_at(Grid& g, const double* xyz, size_t n, uint64_t* ids) {
 	di.alloc(n);
 	h2d(dx.p, xyz, 3 * n * sizeof(double), s);
 	if (g.str.active)
-		stretched_cells_at_kernel<<<grid_for(n, 256), 256, 0, s>>>(g.m, g.dm(), make_sgeo(g), dx.p, n, di.p);
+		cells_at_kernel<SGeo><<<grid_for(n, 256), 256, 0, s>>>(g.m, g.dm(), make_sgeo(g), dx.p, n, di.p);
 	else
-		cells_at_kernel<<<grid_for(n, 256), 256, 0, s>>>(g.m, g.dm(), make_geo(g), dx.p, n, di.p);
+		cells_at_kernel<PGeo><<<grid_for(n, 256), 256, 0, s>>>(g.m, g.dm(), make_geo(g), dx.p, n, di.p);
 	HIP_CHECK(hipGetLastError());
 	d2h_small(ids, di.p, n * sizeof(uint64_t), s);
 }
 
 void particles_step(Grid& g, int fid, int K, const double* velocity, double dt, uint64_t stats[5]) {
 	require_geometry(g);
-	Field& f = field(g, fid);
-	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	ParticleCall P(g, fid);
+	// (K before the call's own rules, as dccrgx_particles_reduce)
 	DX_REQUIRE(K >= 3, "a particle record has at least 3 doubles (the position)");
 	DX_REQUIRE(velocity || K >= 6, "per-particle velocities (velocity == NULL) need records of at least 6 doubles");
 	DX_REQUIRE(stats, "null pointer");
 	for (int k = 0; k < 5; k++) stats[k] = 0;
-	hipStream_t s = g.s_comp;
-	const size_t ns = g.n_slots, nl = g.n_local;
-	if (!ns || !f.voff.p) return;
+	P.prepare(K, 0, false, false);
+	Field& f = P.f;
+	hipStream_t s = P.s;
+	const size_t ns = g.n_slots, nl = g.n_local, N = P.N_all;
 	const uint64_t rec = uint64_t(K) * sizeof(double);
-
-	// record offsets of the slots; every cell a whole number of records
-	DBuf<uint32_t> ofirst;
-	DBuf<int32_t> flag;
-	ofirst.alloc(ns + 1);
-	flag.alloc(1);
-	HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, s));
-	const uint64_t total = var_total(f, ns, s);
-	DX_REQUIRE(total / rec < (uint64_t(1) << 31), "more than 2^31 particles on one process");
-	record_offsets_kernel<<<grid_for(ns + 1, 256), 256, 0, s>>>(f.voff.p, ns + 1, rec, ofirst.p, flag.p);
-	HIP_CHECK(hipGetLastError());
-	int32_t bad = 0;
-	d2h_small(&bad, flag.p, 4, s);
-	DX_REQUIRE(!bad, "a cell's payload is not a multiple of 8 * record_doubles bytes");
-	const size_t N = size_t(total / rec);
+	const DBuf<uint32_t>& ofirst = P.ofirst;
 	if (!N) return;
 	ensure_csr(g);
 
@@ -602,15 +700,11 @@ void particles_step(Grid& g, int fid, int K, const double* velocity, double dt, 
 	mpos.alloc(N + 1);
 	const unsigned nb = grid_for(N, kPB, 8192);
 	part.alloc(4 * size_t(nb));
-	const size_t chunks = (N + kPB - 1) / kPB;
-	DBuf<uint32_t> chunk_slot;
-	chunk_slot.alloc(chunks + 1);
-	chunk_slots_kernel<<<grid_for(chunks + 1, 256), 256, 0, s>>>(ofirst.p, ns, N, chunks, chunk_slot.p);
-	HIP_CHECK(hipGetLastError());
+	P.chunk_slots(ns, N);
 	PArgs a{};
-	a.pool = reinterpret_cast<double*>(f.data.p);
+	a.pool = P.pool();
 	a.ofirst = ofirst.p;
-	a.chunk_slot = chunk_slot.p;
+	a.chunk_slot = P.chunk_slot.p;
 	a.n_slots = ns;
 	a.n_local = nl;
 	a.N = N;
@@ -815,14 +909,8 @@ struct FArgs {
 template <class Geo>
 __global__ __launch_bounds__(kFB) void follow_locate_kernel(const MapCtx m, const DevMesh M, const Geo G,
                                                               const FArgs a) {
-	constexpr bool kStretched = std::is_same<Geo, SGeo>::value;
-	double* s_c = nullptr;
-	bool coords_cached = false;
-	if constexpr (kStretched) {
-		__shared__ double s_coords[kCoordCache];
-		s_c = s_coords;
-		coords_cached = stage_coordinates(G, s_c);
-	}
+	const double* s_c;
+	const bool coords_cached = stage_geometry(G, s_c);
 	// the two counts of a block are added up in LDS, one global atomic per
 	// block and count (one per child of every parent, all on one address,
 	// cost 19 ms at 262 144 parents where the whole carry now takes 0.7 ms)
@@ -845,11 +933,7 @@ __global__ __launch_bounds__(kFB) void follow_locate_kernel(const MapCtx m, cons
 			if (valid) {
 				const double* r = a.pool + (first + r0 + lane) * size_t(a.K);
 				const double x[3] = {r[0], r[1], r[2]};
-				uint64_t leaf;
-				if constexpr (kStretched)
-					leaf = coords_cached ? stretched_cell_at(m, M, G, s_c, x) : stretched_cell_at(m, M, G, G.c, x);
-				else
-					leaf = existing_cell_at(m, M, G, x);
+				const uint64_t leaf = cell_at(m, M, G, s_c, coords_cached, x);
 				c = 8;
 #pragma unroll
 				for (int k = 0; k < 8; k++)
@@ -1266,66 +1350,85 @@ struct DArgs {
 	double* out;
 };
 
+// The walk of one receiving local cell c (id cid) by its wave: the cell's own
+// records 64 at a time, then (CIC) the distinct non-empty leaves of its row
+// four at a time, 16 lanes each.  Every (record, receiver) pair reaches
+// acc.add(rec, q, w) once, q the weight double and w = W(p, c); what the
+// lanes' sums become is the kernel's.
+template <int SHAPE, class Acc>
+__device__ __forceinline__ void deposit_walk(const MapCtx& m, const WGeo& G, const DArgs& a, size_t c, uint64_t cid,
+                                             uint32_t lane, Acc& acc) {
+	const uint32_t grp = lane / kDGroup, gl = lane % kDGroup;
+	CellBox C{};
+	if (SHAPE == 1) cell_box(m, G, cid, C);
+	// the cell's own records
+	for (uint32_t r = a.ofirst[c] + lane, r1 = a.ofirst[c + 1]; r < r1; r += 64) {
+		const double* rec = a.pool + size_t(r) * size_t(a.K);
+		const double q = a.wd < 0 ? 1.0 : rec[a.wd];
+		double w = 1.0;
+		if (SHAPE == 1) {
+			const double x[3] = {rec[0], rec[1], rec[2]};
+			w = cic_weight(G, C, C, x);
+		}
+		acc.add(rec, q, w);
+	}
+	if (SHAPE == 1) {
+		const uint32_t b = a.it_ptr[c], e = a.it_ptr[c + 1];
+		for (uint32_t j0 = b; j0 < e; j0 += 64) {
+			const uint32_t j = j0 + lane;
+			int32_t s = 0;
+			bool take = false;
+			if (j < e) {
+				s = a.it_slot[j];
+				take = s >= 0 && size_t(s) != c && (j == b || a.it_slot[j - 1] != s) &&
+				       a.ofirst[s + 1] != a.ofirst[s];
+			}
+			// the sources of this part of the row, four at a time: group k
+			// takes the (k + 1)-th lane left in `rem`
+			unsigned long long rem = __ballot(take);
+			while (rem) {
+				unsigned long long mine = rem;
+				for (uint32_t k = 0; k < grp; k++) mine &= mine - 1;
+				const int from = mine ? __ffsll(mine) - 1 : 0;
+				const int32_t sg = __shfl(s, from);
+				if (mine) {
+					CellBox S;
+					cell_box(m, G, a.slot_ids[sg], S);
+					for (uint32_t r = a.ofirst[sg] + gl, r1 = a.ofirst[sg + 1]; r < r1; r += kDGroup) {
+						const double* rec = a.pool + size_t(r) * size_t(a.K);
+						const double q = a.wd < 0 ? 1.0 : rec[a.wd];
+						const double x[3] = {rec[0], rec[1], rec[2]};
+						const double w = cic_weight(G, S, C, x);
+						acc.add(rec, q, w);
+					}
+				}
+				for (int k = 0; k < 64 / kDGroup; k++) rem &= rem - 1;
+			}
+		}
+	}
+}
+
+// the deposit's accumulator: one sum of q W
+struct DepositSum {
+	double sum = 0.0;
+	__device__ __forceinline__ void add(const double*, double q, double w) {
+		const double term = q * w;
+		sum = sum + term;
+	}
+};
+
 // (at least six waves per SIMD: the CIC form fits 80 VGPRs without scratch,
 // and its chains of dependent fp64 operations want the waves: 8.85 -> 7.5 ms
 // on the bench's grid against the four waves of 106 VGPRs)
 template <int SHAPE>
 __global__ __launch_bounds__(kDB) __attribute__((amdgpu_waves_per_eu(6))) void particles_deposit_kernel(const MapCtx m, const WGeo G, const DArgs a) {
 	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t grp = lane / kDGroup, gl = lane % kDGroup;
 	const size_t waves = size_t(gridDim.x) * (kDB >> 6);
 	for (size_t c = blockIdx.x * size_t(kDB >> 6) + (threadIdx.x >> 6); c < a.n_local; c += waves) {
 		const uint64_t cid = a.slot_ids[c];
-		CellBox C{};
-		if (SHAPE == 1) cell_box(m, G, cid, C);
-		double sum = 0.0;
-		// the cell's own records
-		for (uint32_t r = a.ofirst[c] + lane, r1 = a.ofirst[c + 1]; r < r1; r += 64) {
-			const double* rec = a.pool + size_t(r) * size_t(a.K);
-			const double q = a.wd < 0 ? 1.0 : rec[a.wd];
-			double w = 1.0;
-			if (SHAPE == 1) {
-				const double x[3] = {rec[0], rec[1], rec[2]};
-				w = cic_weight(G, C, C, x);
-			}
-			const double term = q * w;
-			sum = sum + term;
-		}
-		if (SHAPE == 1) {
-			const uint32_t b = a.it_ptr[c], e = a.it_ptr[c + 1];
-			for (uint32_t j0 = b; j0 < e; j0 += 64) {
-				const uint32_t j = j0 + lane;
-				int32_t s = 0;
-				bool take = false;
-				if (j < e) {
-					s = a.it_slot[j];
-					take = s >= 0 && size_t(s) != c && (j == b || a.it_slot[j - 1] != s) &&
-					       a.ofirst[s + 1] != a.ofirst[s];
-				}
-				// the sources of this part of the row, four at a time: group k
-				// takes the (k + 1)-th lane left in `rem`
-				unsigned long long rem = __ballot(take);
-				while (rem) {
-					unsigned long long mine = rem;
-					for (uint32_t k = 0; k < grp; k++) mine &= mine - 1;
-					const int from = mine ? __ffsll(mine) - 1 : 0;
-					const int32_t sg = __shfl(s, from);
-					if (mine) {
-						CellBox S;
-						cell_box(m, G, a.slot_ids[sg], S);
-						for (uint32_t r = a.ofirst[sg] + gl, r1 = a.ofirst[sg + 1]; r < r1; r += kDGroup) {
-							const double* rec = a.pool + size_t(r) * size_t(a.K);
-							const double q = a.wd < 0 ? 1.0 : rec[a.wd];
-							const double x[3] = {rec[0], rec[1], rec[2]};
-							const double w = cic_weight(G, S, C, x);
-							const double term = q * w;
-							sum = sum + term;
-						}
-					}
-					for (int k = 0; k < 64 / kDGroup; k++) rem &= rem - 1;
-				}
-			}
-		}
+		DepositSum acc;
+		deposit_walk<SHAPE>(m, G, a, c, cid, lane, acc);
+		double sum = acc.sum;
 #pragma unroll
 		for (int o = 32; o > 0; o >>= 1) {
 			const double other = __shfl_down(sum, o);
@@ -1339,7 +1442,7 @@ __global__ __launch_bounds__(kDB) __attribute__((amdgpu_waves_per_eu(6))) void p
 }
 
 // Several moments of the records in one walk (dccrgx_particles_deposit_moments):
-// the deposit's walk, lane for lane and shuffle for shuffle, with W(p, c)
+// the deposit's walk (deposit_walk) and its shuffle tree, with W(p, c)
 // formed once per (record, receiver) and fed to M accumulators.  A call with
 // more moments than kMW runs several passes, full ones first.  (DESIGN.md
 // "Moments in one deposit pass" has the resource report and the measurements
@@ -1378,63 +1481,24 @@ __device__ __forceinline__ void moments_add(const double* rec, double q, double 
 	}
 }
 
+// the moments' accumulator: the M sums of a pass
+template <int M>
+struct MomentSums {
+	const MArgs& f;
+	double sum[M] = {};
+	__device__ __forceinline__ void add(const double* rec, double q, double w) { moments_add<M>(rec, q, w, f, sum); }
+};
+
 template <int SHAPE, int M>
 __global__ __launch_bounds__(kDB) __attribute__((amdgpu_waves_per_eu(moments_waves(M)))) void particles_moments_kernel(
     const MapCtx m, const WGeo G, const DArgs a, const MArgs f) {
 	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t grp = lane / kDGroup, gl = lane % kDGroup;
 	const size_t waves = size_t(gridDim.x) * (kDB >> 6);
 	for (size_t c = blockIdx.x * size_t(kDB >> 6) + (threadIdx.x >> 6); c < a.n_local; c += waves) {
 		const uint64_t cid = a.slot_ids[c];
-		CellBox C{};
-		if (SHAPE == 1) cell_box(m, G, cid, C);
-		double sum[M];
-#pragma unroll
-		for (int j = 0; j < M; j++) sum[j] = 0.0;
-		// the cell's own records
-		for (uint32_t r = a.ofirst[c] + lane, r1 = a.ofirst[c + 1]; r < r1; r += 64) {
-			const double* rec = a.pool + size_t(r) * size_t(a.K);
-			const double q = a.wd < 0 ? 1.0 : rec[a.wd];
-			double w = 1.0;
-			if (SHAPE == 1) {
-				const double x[3] = {rec[0], rec[1], rec[2]};
-				w = cic_weight(G, C, C, x);
-			}
-			moments_add<M>(rec, q, w, f, sum);
-		}
-		if (SHAPE == 1) {
-			const uint32_t b = a.it_ptr[c], e = a.it_ptr[c + 1];
-			for (uint32_t j0 = b; j0 < e; j0 += 64) {
-				const uint32_t j = j0 + lane;
-				int32_t s = 0;
-				bool take = false;
-				if (j < e) {
-					s = a.it_slot[j];
-					take = s >= 0 && size_t(s) != c && (j == b || a.it_slot[j - 1] != s) &&
-					       a.ofirst[s + 1] != a.ofirst[s];
-				}
-				// the sources of this part of the row, four at a time, as the deposit
-				unsigned long long rem = __ballot(take);
-				while (rem) {
-					unsigned long long mine = rem;
-					for (uint32_t k = 0; k < grp; k++) mine &= mine - 1;
-					const int from = mine ? __ffsll(mine) - 1 : 0;
-					const int32_t sg = __shfl(s, from);
-					if (mine) {
-						CellBox S;
-						cell_box(m, G, a.slot_ids[sg], S);
-						for (uint32_t r = a.ofirst[sg] + gl, r1 = a.ofirst[sg + 1]; r < r1; r += kDGroup) {
-							const double* rec = a.pool + size_t(r) * size_t(a.K);
-							const double q = a.wd < 0 ? 1.0 : rec[a.wd];
-							const double x[3] = {rec[0], rec[1], rec[2]};
-							const double w = cic_weight(G, S, C, x);
-							moments_add<M>(rec, q, w, f, sum);
-						}
-					}
-					for (int k = 0; k < 64 / kDGroup; k++) rem &= rem - 1;
-				}
-			}
-		}
+		MomentSums<M> acc{f};
+		deposit_walk<SHAPE>(m, G, a, c, cid, lane, acc);
+		double(&sum)[M] = acc.sum;
 #pragma unroll
 		for (int j = 0; j < M; j++) {
 #pragma unroll
@@ -1456,7 +1520,7 @@ constexpr int kGF = 4;  // cell fields per gather pass
 struct GArgs {
 	double* pool;
 	const uint32_t* ofirst;      // n_local + 1 record offsets
-	const uint32_t* chunk_slot;  // chunks + 1 (chunk_slots_kernel)
+	const uint32_t* chunk_slot;  // chunks + 1 (pass_slots_kernel)
 	size_t N;                    // records of the local cells
 	int K, first, nf;            // nf fields into doubles first ..
 	const uint64_t* slot_ids;
@@ -1472,17 +1536,10 @@ __global__ __launch_bounds__(kPB) void particles_gather_kernel(const MapCtx m, c
 	const size_t chunks = (a.N + kPB - 1) / kPB;
 	for (size_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
 		const size_t p0 = ch * kPB, p1 = p0 + kPB < a.N ? p0 + kPB : a.N;
-		__syncthreads();
-		const size_t lo = a.chunk_slot[ch], hi = a.chunk_slot[ch + 1];
-		const size_t span = hi - lo + 2;
-		const bool cached = span <= size_t(kOffCache);
-		if (cached)
-			for (size_t i = threadIdx.x; i < span; i += kPB) s_off[i] = a.ofirst[lo + i];
-		__syncthreads();
+		const OffsetWindow W = stage_offsets(a.ofirst, a.chunk_slot, ch, s_off);
 		const size_t p = p0 + threadIdx.x;
 		if (p >= p1) continue;
-		const size_t s = cached ? lo + upper_bound_idx<uint32_t>(s_off, 0, span, uint32_t(p)) - 1
-		                        : upper_bound_idx<uint32_t>(a.ofirst, lo, hi + 2, uint32_t(p)) - 1;
+		const size_t s = W.slot(uint32_t(p));
 		double* r = a.pool + p * size_t(a.K);
 		double acc[kGF];
 		if (SHAPE == 0) {
@@ -1518,36 +1575,6 @@ __global__ __launch_bounds__(kPB) void particles_gather_kernel(const MapCtx m, c
 		for (int j = 0; j < kGF; j++)
 			if (j < a.nf) r[a.first + j] = acc[j];
 	}
-}
-
-// the checks the two calls share; the record offsets of every slot (empty: no
-// pool).  Returns the number of records in the pool.
-size_t particle_mesh_prepare(Grid& g, Field& f, int K, int shape, bool lengths, DBuf<uint32_t>& ofirst) {
-	DX_REQUIRE(g.initialized, "not initialized");
-	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
-	DX_REQUIRE(K >= 3, "a particle record has at least 3 doubles (the position)");
-	DX_REQUIRE(shape == 0 || shape == 1, "shape must be 0 (NGP) or 1 (CIC)");
-	if (shape == 1) {
-		DX_REQUIRE(g.hood_len >= 1, "CIC needs a neighborhood length of at least 1");
-		DX_REQUIRE(!g.str.active, "CIC needs a Cartesian geometry (a stretched geometry is set)");
-	}
-	if (shape == 1 || lengths) require_geometry(g);
-	hipStream_t s = g.s_comp;
-	const size_t ns = g.n_slots;
-	if (!ns || !f.voff.p) return 0;
-	const uint64_t rec = uint64_t(K) * sizeof(double);
-	const uint64_t total = var_total(f, ns, s);
-	DX_REQUIRE(total / rec < (uint64_t(1) << 31), "more than 2^31 particles on one process");
-	DBuf<int32_t> flag;
-	ofirst.alloc(ns + 1);
-	flag.alloc(1);
-	HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, s));
-	record_offsets_kernel<<<grid_for(ns + 1, 256), 256, 0, s>>>(f.voff.p, ns + 1, rec, ofirst.p, flag.p);
-	HIP_CHECK(hipGetLastError());
-	int32_t bad = 0;
-	d2h_small(&bad, flag.p, 4, s);
-	DX_REQUIRE(!bad, "a cell's payload is not a multiple of 8 * record_doubles bytes");
-	return size_t(total / rec);
 }
 
 // v += (factor q) E for the first N records of the pool (the local cells'):
@@ -1646,46 +1673,47 @@ Field& fp64_cell_field(Grid& g, int fid, const char* what) {
 	return F;
 }
 
+// the walk's arguments of a prepared call with records (ensure_csr: the rows)
+DArgs make_dargs(const ParticleCall& P, int weight_double, int per_volume, double* out) {
+	ensure_csr(P.g);
+	DArgs a{};
+	a.pool = P.pool();
+	a.ofirst = P.ofirst.p;
+	a.slot_ids = P.g.slot_ids.p;
+	a.it_ptr = P.g.it_ptr.p;
+	a.it_slot = P.g.it_slot.p;
+	a.n_local = P.g.n_local;
+	a.K = P.K;
+	a.wd = weight_double;
+	a.per_volume = per_volume ? 1 : 0;
+	a.out = out;
+	return a;
+}
+
 }  // namespace
 
 void particles_deposit(Grid& g, int fid, int K, int shape, int weight_double, int out_fid, int per_volume) {
-	Field& f = field(g, fid);
-	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	ParticleCall P(g, fid);
 	Field& out = fp64_cell_field(g, out_fid, "the deposit's output");
-	DX_REQUIRE(weight_double == -1 || (weight_double >= 3 && weight_double < K) || K < 3,
-	           "weight_double must be -1 (q = 1) or a double of the record past the position (3 <= weight_double < "
-	           "record_doubles)");
-	DBuf<uint32_t> ofirst;
-	const size_t N = particle_mesh_prepare(g, f, K, shape, per_volume != 0, ofirst);
+	require_weight_double(K, weight_double, 3, "position");
+	P.prepare(K, shape, per_volume != 0, false);
 	const size_t nl = g.n_local;
-	hipStream_t s = g.s_comp;
 	field_written(out);
 	if (!nl) return;
 	double* o = reinterpret_cast<double*>(out.data.p);
-	if (!N) {  // every sum is empty
-		HIP_CHECK(hipMemsetAsync(o, 0, nl * sizeof(double), s));
+	if (!P.N_all) {  // every sum is empty
+		HIP_CHECK(hipMemsetAsync(o, 0, nl * sizeof(double), P.s));
 		return;
 	}
-	ensure_csr(g);
-	DArgs a{};
-	a.pool = reinterpret_cast<const double*>(f.data.p);
-	a.ofirst = ofirst.p;
-	a.slot_ids = g.slot_ids.p;
-	a.it_ptr = g.it_ptr.p;
-	a.it_slot = g.it_slot.p;
-	a.n_local = nl;
-	a.K = K;
-	a.wd = weight_double;
-	a.per_volume = per_volume ? 1 : 0;
-	a.out = o;
+	const DArgs a = make_dargs(P, weight_double, per_volume, o);
 	const WGeo G = make_wgeo(g, per_volume != 0);
 	const unsigned nb = grid_for(nl, kDB >> 6, 1u << 20);
 	if (shape == 1)
-		particles_deposit_kernel<1><<<nb, kDB, 0, s>>>(g.m, G, a);
+		particles_deposit_kernel<1><<<nb, kDB, 0, P.s>>>(g.m, G, a);
 	else
-		particles_deposit_kernel<0><<<nb, kDB, 0, s>>>(g.m, G, a);
+		particles_deposit_kernel<0><<<nb, kDB, 0, P.s>>>(g.m, G, a);
 	HIP_CHECK(hipGetLastError());
-	HIP_CHECK(hipStreamSynchronize(s));  // ofirst goes out of scope
+	P.finish();
 }
 
 namespace {
@@ -1711,8 +1739,7 @@ void moments_launch(int width, int shape, unsigned nb, hipStream_t s, const MapC
 
 void particles_deposit_moments(Grid& g, int fid, int K, int shape, int weight_double, const int* factors,
                                const int* out_fids, int n, int per_volume) {
-	Field& f = field(g, fid);
-	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	ParticleCall P(g, fid);
 	DX_REQUIRE(n >= 1 && n <= 16, "the number of moments must be 1 .. 16");
 	DX_REQUIRE(factors && out_fids, "null pointer");
 	std::vector<double*> outs;
@@ -1722,35 +1749,21 @@ void particles_deposit_moments(Grid& g, int fid, int K, int shape, int weight_do
 			DX_REQUIRE(out_fids[i] != out_fids[j], "two moments share an output field");
 		outs.push_back(reinterpret_cast<double*>(o.data.p));
 	}
-	DX_REQUIRE(weight_double == -1 || (weight_double >= 3 && weight_double < K) || K < 3,
-	           "weight_double must be -1 (q = 1) or a double of the record past the position (3 <= weight_double < "
-	           "record_doubles)");
+	require_weight_double(K, weight_double, 3, "position");
 	for (int j = 0; j < 2 * n; j++)
 		DX_REQUIRE(factors[j] == -1 || (factors[j] >= 3 && factors[j] < K) || K < 3,
 		           "a moment factor must be -1 (1.0) or a double of the record past the position (3 <= factor < "
 		           "record_doubles)");
-	DBuf<uint32_t> ofirst;
-	const size_t N = particle_mesh_prepare(g, f, K, shape, per_volume != 0, ofirst);
+	P.prepare(K, shape, per_volume != 0, false);
 	const size_t nl = g.n_local;
-	hipStream_t s = g.s_comp;
+	hipStream_t s = P.s;
 	for (int j = 0; j < n; j++) field_written(fixed_field(g, out_fids[j]));
 	if (!nl) return;
-	if (!N) {  // every sum is empty
+	if (!P.N_all) {  // every sum is empty
 		for (int j = 0; j < n; j++) HIP_CHECK(hipMemsetAsync(outs[size_t(j)], 0, nl * sizeof(double), s));
 		return;
 	}
-	ensure_csr(g);
-	DArgs a{};
-	a.pool = reinterpret_cast<const double*>(f.data.p);
-	a.ofirst = ofirst.p;
-	a.slot_ids = g.slot_ids.p;
-	a.it_ptr = g.it_ptr.p;
-	a.it_slot = g.it_slot.p;
-	a.n_local = nl;
-	a.K = K;
-	a.wd = weight_double;
-	a.per_volume = per_volume ? 1 : 0;
-	a.out = nullptr;
+	const DArgs a = make_dargs(P, weight_double, per_volume, nullptr);
 	const WGeo G = make_wgeo(g, per_volume != 0);
 	const unsigned nb = grid_for(nl, kDB >> 6, 1u << 20);
 	for (int j0 = 0; j0 < n; j0 += kMW) {
@@ -1765,12 +1778,11 @@ void particles_deposit_moments(Grid& g, int fid, int K, int shape, int weight_do
 		moments_launch<kMW>(width, shape, nb, s, g.m, G, a, ma);
 		HIP_CHECK(hipGetLastError());
 	}
-	HIP_CHECK(hipStreamSynchronize(s));  // ofirst goes out of scope
+	P.finish();
 }
 
 void particles_gather(Grid& g, int fid, int K, int shape, const int* cell_fields, int n, int first_double) {
-	Field& f = field(g, fid);
-	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	ParticleCall P(g, fid);
 	DX_REQUIRE(n >= 1 && cell_fields, "gather needs at least one cell field");
 	std::vector<const double*> F;
 	for (int j = 0; j < n; j++)
@@ -1778,23 +1790,16 @@ void particles_gather(Grid& g, int fid, int K, int shape, const int* cell_fields
 	DX_REQUIRE(K < 3 || (first_double >= 3 && first_double + n <= K),
 	           "the gathered doubles must lie in the record past the position (3 <= first_double, first_double + n <= "
 	           "record_doubles)");
-	DBuf<uint32_t> ofirst;
-	const size_t N_all = particle_mesh_prepare(g, f, K, shape, false, ofirst);
-	const size_t nl = g.n_local;
-	hipStream_t s = g.s_comp;
-	if (!N_all || !nl) return;
-	const size_t N = size_t(var_total(f, nl, s) / (uint64_t(K) * sizeof(double)));  // the local cells' records
+	P.prepare(K, shape, false, true);
+	const size_t N = P.N_local;
+	hipStream_t s = P.s;
 	if (!N) return;
 	ensure_csr(g);
-	const size_t chunks = (N + kPB - 1) / kPB;
-	DBuf<uint32_t> chunk_slot;
-	chunk_slot.alloc(chunks + 1);
-	chunk_slots_kernel<<<grid_for(chunks + 1, 256), 256, 0, s>>>(ofirst.p, nl, N, chunks, chunk_slot.p);
-	HIP_CHECK(hipGetLastError());
+	P.chunk_slots(g.n_local, N);
 	GArgs a{};
-	a.pool = reinterpret_cast<double*>(f.data.p);
-	a.ofirst = ofirst.p;
-	a.chunk_slot = chunk_slot.p;
+	a.pool = P.pool();
+	a.ofirst = P.ofirst.p;
+	a.chunk_slot = P.chunk_slot.p;
 	a.N = N;
 	a.K = K;
 	a.slot_ids = g.slot_ids.p;
@@ -1817,38 +1822,28 @@ void particles_gather(Grid& g, int fid, int K, int shape, const int* cell_fields
 			particles_gather_kernel<0><<<nb, kPB, 0, s>>>(g.m, G, a);
 		HIP_CHECK(hipGetLastError());
 	}
-	field_written(f);
-	HIP_CHECK(hipStreamSynchronize(s));  // ofirst and chunk_slot go out of scope
+	field_written(P.f);
+	P.finish();
 }
 
 void particles_accelerate(Grid& g, int fid, int K, int first_double, int weight_double, double factor) {
-	Field& f = field(g, fid);
-	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	ParticleCall P(g, fid);
 	DX_REQUIRE(K < 3 || (first_double >= 6 && first_double + 3 <= K),
 	           "the field's three doubles must lie in the record past the velocity (6 <= first_double, first_double + 3 "
 	           "<= record_doubles)");
-	DX_REQUIRE(K < 3 || weight_double == -1 ||
-	               (weight_double >= 6 && weight_double < K &&
-	                !(weight_double >= first_double && weight_double < first_double + 3)),
-	           "weight_double must be -1 (q = 1) or a double of the record past the velocity and outside the field's "
-	           "three (6 <= weight_double < record_doubles)");
-	DBuf<uint32_t> ofirst;
-	const size_t N_all = particle_mesh_prepare(g, f, K, 0, false, ofirst);
-	const size_t nl = g.n_local;
-	hipStream_t s = g.s_comp;
-	if (!N_all || !nl) return;
-	const size_t N = size_t(var_total(f, nl, s) / (uint64_t(K) * sizeof(double)));  // the local cells' records
+	require_weight_double(K, weight_double, 6, "velocity and outside the field's three", {first_double});
+	P.prepare(K, 0, false, true);
+	const size_t N = P.N_local;
 	if (!N) return;
-	particles_accelerate_kernel<<<grid_for(N, kPB, 1u << 20), kPB, 0, s>>>(reinterpret_cast<double*>(f.data.p), N, K,
-	                                                                       first_double, weight_double, factor);
+	particles_accelerate_kernel<<<grid_for(N, kPB, 1u << 20), kPB, 0, P.s>>>(P.pool(), N, K, first_double, weight_double,
+	                                                                         factor);
 	HIP_CHECK(hipGetLastError());
-	field_written(f);
-	HIP_CHECK(hipStreamSynchronize(s));  // ofirst goes out of scope
+	field_written(P.f);
+	P.finish();
 }
 
 void particles_boris(Grid& g, int fid, int K, int e_first, int b_first, int weight_double, double factor) {
-	Field& f = field(g, fid);
-	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	ParticleCall P(g, fid);
 	DX_REQUIRE(K < 3 || (e_first >= 6 && e_first + 3 <= K),
 	           "E's three doubles must lie in the record past the velocity (6 <= e_first, e_first + 3 <= "
 	           "record_doubles)");
@@ -1857,24 +1852,15 @@ void particles_boris(Grid& g, int fid, int K, int e_first, int b_first, int weig
 	           "record_doubles)");
 	DX_REQUIRE(K < 3 || b_first >= e_first + 3 || e_first >= b_first + 3,
 	           "E's and B's doubles overlap (e_first and b_first must be at least 3 apart)");
-	DX_REQUIRE(K < 3 || weight_double == -1 ||
-	               (weight_double >= 6 && weight_double < K &&
-	                !(weight_double >= e_first && weight_double < e_first + 3) &&
-	                !(weight_double >= b_first && weight_double < b_first + 3)),
-	           "weight_double must be -1 (q = 1) or a double of the record past the velocity and outside E's and B's "
-	           "three (6 <= weight_double < record_doubles)");
-	DBuf<uint32_t> ofirst;
-	const size_t N_all = particle_mesh_prepare(g, f, K, 0, false, ofirst);
-	const size_t nl = g.n_local;
-	hipStream_t s = g.s_comp;
-	if (!N_all || !nl) return;
-	const size_t N = size_t(var_total(f, nl, s) / (uint64_t(K) * sizeof(double)));  // the local cells' records
+	require_weight_double(K, weight_double, 6, "velocity and outside E's and B's three", {e_first, b_first});
+	P.prepare(K, 0, false, true);
+	const size_t N = P.N_local;
 	if (!N) return;
-	particles_boris_kernel<<<grid_for(N, kPB, 1u << 20), kPB, 0, s>>>(reinterpret_cast<double*>(f.data.p), N, K, e_first,
-	                                                                  b_first, weight_double, factor);
+	particles_boris_kernel<<<grid_for(N, kPB, 1u << 20), kPB, 0, P.s>>>(P.pool(), N, K, e_first, b_first, weight_double,
+	                                                                    factor);
 	HIP_CHECK(hipGetLastError());
-	field_written(f);
-	HIP_CHECK(hipStreamSynchronize(s));  // ofirst goes out of scope
+	field_written(P.f);
+	P.finish();
 }
 
 // up to 16 reductions over the records of the local cells, the results in
@@ -1884,14 +1870,11 @@ void particles_boris(Grid& g, int fid, int K, int e_first, int b_first, int weig
 // waits on the host.
 void particles_reduce(Grid& g, int fid, int K, int weight_double, const int* terms, int n, int collective,
                       double* d_out) {
-	Field& f = field(g, fid);
-	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	ParticleCall P(g, fid);
 	DX_REQUIRE(n >= 1 && n <= kRedTerms, "the number of terms must be 1 .. 16");
 	DX_REQUIRE(terms && d_out, "null pointer");
 	DX_REQUIRE(K >= 3, "a particle record has at least 3 doubles (the position)");
-	DX_REQUIRE(weight_double == -1 || (weight_double >= 3 && weight_double < K),
-	           "weight_double must be -1 (q = 1) or a double of the record past the position (3 <= weight_double < "
-	           "record_doubles)");
+	require_weight_double(K, weight_double, 3, "position");
 	RedArgs T;
 	RedDoubles D{};
 	T.n = n;
@@ -1916,19 +1899,15 @@ void particles_reduce(Grid& g, int fid, int K, int weight_double, const int* ter
 		cops[j] = red_combine_op(op);
 	}
 	if (collective && g.size > 1) comm_require(g, "a collective reduction");
-	DBuf<uint32_t> ofirst;
-	const size_t N_all = particle_mesh_prepare(g, f, K, 0, false, ofirst);
-	const size_t nl = g.n_local;
-	hipStream_t s = g.s_comp;
-	size_t N = 0;
-	if (N_all && nl) N = size_t(var_total(f, nl, s) / (uint64_t(K) * sizeof(double)));  // the local cells' records
+	P.prepare(K, 0, false, true);
+	const size_t N = P.N_local;
+	hipStream_t s = P.s;
 	const unsigned nb = N ? grid_for(N, kRP, 4096) : 0;
 	k_time_begin(g);
 	if (nb) {
 		g.red_part.reserve(size_t(nb) * kRedTerms);
 		const size_t lds = std::max(size_t(T.nv) * kRP, size_t(kRedTerms) * (kRP / 64)) * sizeof(double);
-		particles_reduce_kernel<<<nb, kRP, lds, s>>>(reinterpret_cast<const double*>(f.data.p), N, K, T, D,
-		                                             g.red_part.p);
+		particles_reduce_kernel<<<nb, kRP, lds, s>>>(P.pool(), N, K, T, D, g.red_part.p);
 		HIP_CHECK(hipGetLastError());
 	}
 	k_reduce_fold(T, g.red_part.p, nb, d_out, s);
@@ -1976,6 +1955,7 @@ RedVolume reduce_volume(Grid& g, bool by_volume) {
 namespace {
 
 constexpr int kCB = 256;  // doubles per block pass
+static_assert(kCB == kPB, "stage_offsets copies with a block of kPB threads");
 
 struct CRecipe {
 	const double *fa, *fb;  // cell fields scaling a and b (nullptr: none)
@@ -1995,7 +1975,7 @@ struct CArgs {
 	double* pool;
 	const uint64_t* noff;        // byte offsets of the new layout
 	const uint32_t* nfirst;      // n_local + 1: first new record of every local slot, all new records numbered through
-	const uint32_t* tile_slot;   // tiles + 1 (create_tile_slots_kernel)
+	const uint32_t* tile_slot;   // tiles + 1 (pass_slots_kernel)
 	const uint64_t* slot_ids;
 	const CRecipe* recipe;       // K entries
 	size_t Nd;                   // doubles to write: new records * K
@@ -2041,15 +2021,6 @@ __global__ void create_first_kernel(const uint64_t* __restrict__ noff, const uin
                                     uint64_t rec, uint32_t* __restrict__ nfirst) {
 	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x)
 		nfirst[i] = uint32_t((noff[i] - ooff[i]) / rec);
-}
-
-// slot of the first double's record of every block pass (and, last entry, of the last record)
-__global__ void create_tile_slots_kernel(const uint32_t* __restrict__ nfirst, size_t n_local, size_t N, uint32_t K,
-                                         size_t tiles, uint32_t* __restrict__ tile_slot) {
-	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i <= tiles; i += size_t(gridDim.x) * blockDim.x) {
-		const size_t p = i < tiles ? (i * kCB) / K : N - 1;
-		tile_slot[i] = uint32_t(upper_bound_idx<uint32_t>(nfirst, 0, n_local + 1, uint32_t(p)) - 1);
-	}
 }
 
 // the next double towards -inf of a finite value
@@ -2110,23 +2081,14 @@ __global__ __launch_bounds__(kCB) void particles_create_kernel(const MapCtx m, c
 		const size_t d0 = t * kCB;
 		const size_t r0 = d0 / a.K;  // the same in every lane
 		const uint32_t j0 = uint32_t(d0 - r0 * a.K);
-		__syncthreads();
-		// the slots of the pass's first and last record bound every search
-		const size_t lo = a.tile_slot[t], hi = a.tile_slot[t + 1];
-		const size_t span = hi - lo + 2;  // offsets lo .. hi + 1
-		const bool cached = span <= size_t(kOffCache);
-		if (cached)
-			for (size_t i = threadIdx.x; i < span; i += kCB) s_off[i] = a.nfirst[lo + i];
-		__syncthreads();
+		const OffsetWindow W = stage_offsets(a.nfirst, a.tile_slot, t, s_off);
 		if (d0 + threadIdx.x >= a.Nd) continue;
 		const uint32_t within = j0 + threadIdx.x;
 		const uint32_t dr = within / a.K;
 		const uint32_t j = within - dr * a.K;
 		const uint32_t r = uint32_t(r0) + dr;
-		const size_t c = cached ? lo + upper_bound_idx<uint32_t>(s_off, 0, span, r) - 1
-		                        : upper_bound_idx<uint32_t>(a.nfirst, lo, hi + 2, r) - 1;
-		const uint32_t f0 = cached ? s_off[c - lo] : a.nfirst[c];
-		const uint32_t f1 = cached ? s_off[c - lo + 1] : a.nfirst[c + 1];
+		const size_t c = W.slot(r);
+		const uint32_t f0 = W.at(c), f1 = W.at(c + 1);
 		const uint32_t i = r - f0;
 		// the cell's new records end where its bytes end
 		double* dst = a.pool + (a.noff[c + 1] / 8 - size_t(f1 - f0) * a.K) + size_t(i) * a.K + j;
@@ -2247,10 +2209,7 @@ void particles_create(Grid& g, int fid, int K, int count_field, double count, in
 	HIP_CHECK(hipGetLastError());
 	const size_t Nd = size_t(N) * size_t(K);
 	const size_t tiles = (Nd + kCB - 1) / kCB;
-	tile_slot.alloc(tiles + 1);
-	create_tile_slots_kernel<<<grid_for(tiles + 1, 256), 256, 0, s>>>(nfirst.p, nl, size_t(N), uint32_t(K), tiles,
-	                                                                tile_slot.p);
-	HIP_CHECK(hipGetLastError());
+	launch_pass_slots(nfirst.p, nl, size_t(N), tiles, size_t(K), tile_slot, s);
 	drc.alloc(size_t(K));
 	h2d(drc.p, rc.data(), size_t(K) * sizeof(CRecipe), s);
 	CGeo G{};

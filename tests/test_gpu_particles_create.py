@@ -130,6 +130,24 @@ def test_bitwise_against_the_model(refined_case):
         assert np.all(r[:, 8] == 0.0)
 
 
+def test_two_full_cells_at_the_ends_of_a_row_of_empty_ones(gpu):
+    """The record search's direct branch: the one block pass of the generate
+    kernel holds the records of the first and of the last local slot, so its
+    window of the new records' offsets is 1 201 entries, more than the 1 024
+    a block keeps in LDS, and every double finds its cell in global memory."""
+    g, m, fld = _pair((1200, 1, 1), periodic=(False, False, False), K=4)
+    ids = _local_ids(g)
+    assert ids.size == 1200 == g.n_slots
+    n = np.zeros(ids.size, np.int64)
+    n[0] = n[-1] = 1  # in slot order: 1 198 empty slots between the two records of the pass
+    cnt = _cell_field(g, "cnt", {int(c): float(k) for c, k in zip(ids, n)})
+    rec = {3: ("uniform", -2.0, 4.0)}
+    assert g.particles_create(fld, 4, count=1.0, count_field=cnt, recipe=rec, seed=0xFACADE) == 2
+    exp, zz = _model(g, ids, n, 4, rec, 0xFACADE)
+    _assert_created(_local_cells(g, fld, 4), exp, zz, 4)
+    g.close()
+
+
 def test_append_keeps_the_lists_and_repeats_with_the_seed(refined_case):
     c = refined_case
     g, fld, ids = c["g"], c["fld"], c["ids"]
