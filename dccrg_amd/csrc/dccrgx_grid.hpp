@@ -25,6 +25,12 @@ void halo_place_peer(Grid& g, int hood, int peer, const uint8_t* buf, size_t byt
 void halo_message_size(Grid& g, int hood, int peer, size_t& sb, size_t& rb);
 
 void stop_refining_impl(Grid& g);  // the created cells in Grid::new_cells
+// the requests stop_refining takes: the status the ABI returns (ENOTFOUND by
+// value for a refused cell, so dccrgx_last_error stays as it was);
+// flush_bulk_requests merges the bulk request lists into the sets first
+void flush_bulk_requests(Grid& g);
+int refine_completely(Grid& g, uint64_t cell);
+int unrefine_completely(Grid& g, uint64_t cell);
 
 void initialize_balance_load_impl(Grid& g, bool use_partitioner, const uint64_t* cells, const int32_t* procs,
                                   size_t n);
@@ -40,6 +46,21 @@ void migration_place_peer(Grid& g, int peer, const uint8_t* buf, size_t bytes);
 std::vector<uint64_t> cells_by_criteria(Grid& g, const int32_t* crit, size_t nc, bool exact, int hood);
 int64_t host_slot_of(Grid& g, uint64_t id);
 bool gol_slab_plan(Grid& g, std::vector<GolBox>& inner, std::vector<GolBox>& outer);
+
+// advection.hip: the advection solver's driver, one function per
+// dccrgx_advection_* entry point of dccrgx.h (fids: rho vx vy vz lx ly lz)
+void advection_step(Grid& g, const int fids[7], double dt, int region);
+void advection_layout(Grid& g, uint64_t out[12]);
+void advection_occupancy(Grid& g, uint64_t out[6]);
+void advection_length_source(Grid& g, const int fids[7], int* out);
+void advection_commit(Grid& g, int df);
+void advection_initialize(Grid& g, const int fids[7]);
+void advection_max_time_step(Grid& g, const int fids[7], double* out);
+void advection_max_time_step_device(Grid& g, const int fids[7], double* d_out);
+std::vector<uint64_t> advection_refine_candidates(Grid& g, int df, double diff_increase, double diff_threshold);
+void advection_check_adaptation(Grid& g, int df, double diff_increase, double diff_threshold,
+                                double unrefine_sensitivity, uint64_t counts[3]);
+void advection_adapt(Grid& g, const int fids[7], uint64_t out[2]);
 
 // particles.hip: the smallest known leaf at each of n host coordinates
 // (error_cell: none), and one push / locate / re-bin step of a variable field

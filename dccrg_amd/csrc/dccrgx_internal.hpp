@@ -356,6 +356,62 @@ inline void field_written(Field& f) {
 // a write of the field's remote copies only (halo receives)
 inline void field_halo_written(Field& f) { f.epoch++; }
 
+struct Grid;
+Field& field(Grid& g, int fid);  // grid.hip; EINVAL for an id that is no field
+
+// N fields as they were at one moment: what a cache derived from field
+// contents (Grid::DtCache, NbRecords, LenTable, BandRec) keeps beside its own
+// conditions, so that "built from these fields as they are now" is one rule.
+template <int N>
+struct FieldKey {
+	struct {
+		int fid = -1;
+		uint64_t epoch = 0, local_epoch = 0;
+		const void* ptr = nullptr;
+	} f[N];
+	// take: records fields fids[0 .. N) as they are now: id, both write
+	// epochs, array.
+	void take(Grid& g, const int* fids) {
+		for (int k = 0; k < N; k++) {
+			const Field& F = field(g, fids[k]);
+			f[k] = {fids[k], F.epoch, F.local_epoch, F.data.p};
+		}
+	}
+	// same: the key was taken from these ids and each field has the array and
+	// the write epoch it had then - no write since that the library made or
+	// was asked to make (a rebuild moves the array and bumps the epoch
+	// together, mesh.hip rebuild, so the array alone never turns a hit into a
+	// miss).  local: local_epoch in place of epoch, for a cache that reads no
+	// remote copy (halo receives then leave it standing).
+	bool same(Grid& g, const int* fids, bool local = false) const {
+		for (int k = 0; k < N; k++) {
+			const Field& F = field(g, fids[k]);
+			if (f[k].fid != fids[k] || f[k].ptr != F.data.p) return false;
+			if (local ? f[k].local_epoch != F.local_epoch : f[k].epoch != F.epoch) return false;
+		}
+		return true;
+	}
+	// trackable: no field is external.  A field whose device pointer was
+	// handed out is written unseen, so no cache is built from it or believed
+	// until the next structural change voids the pointer.
+	static bool trackable(Grid& g, const int* fids) {
+		for (int k = 0; k < N; k++)
+			if (field(g, fids[k]).external) return false;
+		return true;
+	}
+};
+
+// sets `ref` to `now` and writes the value it had back when the scope ends,
+// by return or by exception
+template <class T>
+struct Restore {
+	T& ref;
+	const T saved;
+	Restore(T& r, T now) : ref(r), saved(r) { ref = now; }
+	~Restore() { ref = saved; }
+	Restore(const Restore&) = delete;
+};
+
 // the active stretched geometry as the built-in solvers' kernels take it: the
 // packed device coordinates (stretched_device) and each dimension's offset
 // into them; c == nullptr: the grid is Cartesian
@@ -672,13 +728,12 @@ struct Grid {
 	size_t pin_stage_cap = 0;
 	DBuf<double> dt_part;  // block minima of the advection time step (dt_cache)
 	// the block minima in dt_part are those of the velocity / length fields
-	// fid with these write epochs over n_local cells (nb of them): the time
+	// of `key` as they were then, over n_local cells (nb of them): the time
 	// step of advection_adapt's reset pass (fused into it), or of the last
 	// max_time_step, reused until one of the fields is written again
 	struct DtCache {
 		bool valid = false;
-		int fid[6] = {-1, -1, -1, -1, -1, -1};
-		uint64_t epoch[6] = {0, 0, 0, 0, 0, 0};
+		FieldKey<6> key;
 		size_t n_local = 0, nb = 0;
 	} dt_cache;
 	// check_for_adaptation's bands computed by the face-table sweep
@@ -689,8 +744,8 @@ struct Grid {
 	DBuf<uint8_t> band_cache;
 	struct BandRec {
 		bool valid = false;
-		uint64_t face_gen = 0, epoch = 0, local_epoch = 0;
-		const void* rho = nullptr;
+		uint64_t face_gen = 0;
+		FieldKey<1> key;  // the density
 	} band_rec[2];
 	bool band_params_valid = false;
 	double band_inc = 0, band_thr = 0, band_uns = 0;
@@ -774,9 +829,7 @@ struct Grid {
 	// epochs and arrays and the tiles are unchanged.
 	struct NbRecords {
 		DBuf<double> r;
-		int fid[6] = {-1, -1, -1, -1, -1, -1};
-		uint64_t epoch[6] = {0, 0, 0, 0, 0, 0};
-		const void* ptr[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+		FieldKey<6> key;
 		uint64_t tiles_gen = 0;
 		size_t n_slots = 0;
 		bool valid = false;
@@ -791,9 +844,7 @@ struct Grid {
 		DBuf<double> tab;  // 32 rows of (lx, ly, lz)
 		DBuf<int> flag;
 		double tab_l0[3] = {0, 0, 0};  // the level-0 lengths `tab` holds
-		int fid[3] = {-1, -1, -1};
-		uint64_t epoch[3] = {0, 0, 0};
-		const void* ptr[3] = {nullptr, nullptr, nullptr};
+		FieldKey<3> key;
 		uint64_t tiles_gen = 0;
 		size_t n_slots = 0;
 		double l0[3] = {0, 0, 0};
@@ -1106,7 +1157,7 @@ void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int r
 // by one device pass and cached (Grid::LenTable); nullptr - the sweeps read
 // the length fields - otherwise, when a length field is external, a stretched
 // geometry is held, DCCRGX_LEN_TABLE=0, or an experiment variant of the tile
-// kernels is selected.  sweep: the call precedes a sweep (a key found changed
+// kernels is selected (advection.hip).  sweep: the call precedes a sweep (a key found changed
 // at two sweeps in a row backs off to the fields without checking)
 const double* ensure_len_table(Grid& g, const int fids[7], bool sweep);
 // 1 when a slot's lengths differ from its level's row of tab (else 0) into flag
@@ -1146,7 +1197,7 @@ void k_tile_levels(const uint8_t* slot_lvl, const uint32_t* ext_pk, size_t n_ext
 const Grid::SweepLaunch& adv_sweep_launch(Grid& g, int kind, bool nbrec, bool lentab);
 // the neighbor records for the sweep of fields fids (rho vx vy vz lx ly lz),
 // rebuilt when stale; nullptr when a velocity / length field is external
-// (or DCCRGX_NBREC=0): the sweeps then read the fields
+// (or DCCRGX_NBREC=0): the sweeps then read the fields (advection.hip)
 const double* ensure_nbrec(Grid& g, const int fids[7]);
 void k_nbrec(const double* const f[7], size_t n, double* r, hipStream_t s);
 // the bands of check_for_adaptation (adv_bands_kernel) written by the sweep

@@ -567,6 +567,86 @@ static void k_moving_children(Grid& g, const uint64_t* dF, size_t nf, std::map<i
 	DX_REQUIRE(false, "internal error: moving children beyond their count");
 }
 
+void flush_bulk_requests(Grid& g) {
+	g.refine_dev_valid = false;
+	g.refine_dev.release();
+	g.unrefine_dev_valid = false;
+	g.unrefine_dev.release();
+	g.refine_requests.insert(g.refine_bulk.begin(), g.refine_bulk.end());
+	g.unrefine_requests.insert(g.unrefine_bulk.begin(), g.unrefine_bulk.end());
+	g.refine_bulk.clear();
+	g.unrefine_bulk.clear();
+}
+
+// refine_completely (2434-2530): only local leaves; at the maximum level it
+// is dont_unrefine (2472-2475); refused (false) when the cell, or a coarser
+// neighbor of it, is in the dont_refine set that persists from the last
+// stop_refining (2477-2491)
+int refine_completely(Grid& g, uint64_t cell) {
+	DX_REQUIRE(g.initialized, "not initialized");
+	flush_bulk_requests(g);
+	if (!is_local_cell(g, cell)) return DCCRGX_ENOTFOUND;  // 2449-2459: only local cells
+	const int lvl = map_level(g.m, cell);
+	if (lvl >= g.R) {
+		// 2472-2475: dont_unrefine (2679-2733) and true
+		if (lvl == 0) return 0;
+		uint64_t sib[8];
+		map_siblings(g.m, cell, sib);
+		for (uint64_t s : sib)
+			if (g.dont_unrefine_cells.count(s)) return 0;
+		for (uint64_t s : sib) g.unrefine_requests.erase(s);
+		g.dont_unrefine_cells.insert(cell);
+		return 0;
+	}
+	if (!g.dont_refine_cells.empty()) {
+		if (g.dont_refine_cells.count(cell)) return DCCRGX_ENOTFOUND;
+		// a coarser neighbors_of entry in the set (2480-2490): per hood item
+		// the level lvl - 1 leaf holding the item box's min corner (nof_item:
+		// the coarser neighbor of a 2:1-balanced mesh), tested against the
+		// set first and looked up only when it is in it (not a
+		// walk of the whole set per call)
+		if (lvl > 0) {
+			uint64_t c[3];
+			map_indices(g.m, cell, c[0], c[1], c[2]);
+			const int64_t len = int64_t(1) << (g.R - lvl);
+			for (size_t k = 0; k + 2 < g.hood.size(); k += 3) {
+				uint64_t w[3];
+				bool inside = true;
+				for (int a = 0; a < 3 && inside; a++)
+					inside = map_wrap(g.m, a, int64_t(c[a]) + int64_t(g.hood[k + size_t(a)]) * len, w[a]);
+				if (!inside) continue;
+				const uint64_t pl = uint64_t(len) * 2;
+				const uint64_t p = map_from_indices(g.m, w[0] & ~(pl - 1), w[1] & ~(pl - 1), w[2] & ~(pl - 1), lvl - 1);
+				if (g.dont_refine_cells.count(p) && lookup_owner(g, p) >= 0) return DCCRGX_ENOTFOUND;
+			}
+		}
+	}
+	g.refine_requests.insert(cell);
+	return 0;
+}
+
+// unrefine_completely (2560-2660): local leaves only; level 0 is a no-op;
+// false (ENOTFOUND) when a sibling has children; a family marked by a
+// refine or dont_unrefine of a sibling, or already requested, is a no-op.
+// The neighborhood test happens in stop_refining (override_unrefines).
+int unrefine_completely(Grid& g, uint64_t cell) {
+	DX_REQUIRE(g.initialized, "not initialized");
+	if (!is_local_cell(g, cell)) return DCCRGX_ENOTFOUND;
+	if (map_level(g.m, cell) == 0) return 0;
+	flush_bulk_requests(g);
+	uint64_t sib[8];
+	map_siblings(g.m, cell, sib);
+	auto has = [](const std::unordered_set<uint64_t>& v, uint64_t x) { return v.count(x) > 0; };
+	for (uint64_t s : sib) {  // 2596-2607, sibling by sibling
+		if (lookup_owner(g, s) < 0) return DCCRGX_ENOTFOUND;  // the sibling has children
+		if (has(g.refine_requests, s) || has(g.dont_unrefine_cells, s)) return 0;
+	}
+	for (uint64_t s : sib)
+		if (has(g.unrefine_requests, s)) return 0;  // 2636-2641
+	g.unrefine_requests.insert(cell);
+	return 0;
+}
+
 // stop_refining (3461-3485) = override_refines, induce_refines,
 // override_unrefines, execute_refines, distributed:
 //  * override_refines (9991-10038): dont_refine cells spread to their finer

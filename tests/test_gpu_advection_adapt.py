@@ -8,12 +8,16 @@ the oracle's after every step, dt agrees bitwise, densities within
 import numpy as np
 import pytest
 
+import dccrg_amd
 from oracle import oracle as O
 from test_gpu_advection import gpu_grid, prerefine
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-12
+# test_check_declining_a_family_leaves_last_error's counts per view, recorded
+# from the library before the advection driver moved out of the ABI file
+PARENT_COUNTS = [(0, 0, 5), (0, 0, 1)]
 
 
 def product_step(g, f, dt, di):
@@ -168,3 +172,54 @@ def test_kept_children_order_without_sort(gpu, monkeypatch):
     assert merged > 0
     for g, _ in grids:
         g.close()
+
+
+def test_check_declining_a_family_leaves_last_error(gpu):
+    """advection_check_adaptation on two detached views (z-slabs by level-0
+    parent) of a (4, 4, 2) mesh in which one level-0 cell is refined and one
+    of its children again, the density zero everywhere, so every family is
+    all band 0.  A family all of whose members are leaves is requested for
+    unrefinement; the refined child's seven siblings are a partial family whose
+    unrefine_completely answers not-found (a sibling has children): it is not
+    counted, and being declined is no error - dccrgx_last_error still holds
+    the text of the refused call made before."""
+    base, R, P = (4, 4, 2), 2, 2
+    ref = dccrg_amd.Dccrg(0, 1, 0).set_initial_length(base).set_neighborhood_length(0)
+    ref.set_maximum_refinement_level(R).set_periodic(True, True, False).initialize()
+    ref.refine_completely(6)
+    children = ref.stop_refining()
+    assert len(children) == 8
+    ref.refine_completely(int(np.max(children)))
+    assert len(ref.stop_refining()) >= 8
+    leaves = np.sort(ref.local_cells())
+    maps = ref.mapping_batch(leaves)
+    l0p = np.array([ref.get_cell_from_indices(ref.get_indices(int(c)), 0) for c in leaves], np.int64)
+    ref.close()
+    owners = ((l0p - 1) * P // int(np.prod(base))).astype(np.int32)
+    # the model: per view the families (leaves of one parent) with all eight members leaves
+    expected, declined = [], 0
+    for r in range(P):
+        mine = (owners == r) & (maps["level"] > 0)
+        _, members = np.unique(maps["parent"][mine], return_counts=True)
+        assert not np.any(np.isin(maps["parent"][mine], maps["parent"][(owners != r) & (maps["level"] > 0)]))  # none is split
+        expected.append((0, 0, int(np.count_nonzero(members == 8))))
+        declined += int(np.count_nonzero(members < 8))
+    assert declined == 1
+    L = dccrg_amd.lib()
+    assert L.dccrgx_initialize(None) == dccrg_amd._lib.EINVAL
+    before = L.dccrgx_last_error()
+    assert b"null grid" in before
+    got = []
+    for r in range(P):
+        g = dccrg_amd.Dccrg(r, P, 0).set_initial_length(base).set_neighborhood_length(0)
+        g.set_maximum_refinement_level(R).set_periodic(True, True, False).initialize()
+        g.set_geometry((0, 0, 0), tuple(1.0 / b for b in base))
+        rho = g.add_field("density", np.float64, True)
+        g.set_cells(leaves, owners)
+        rho.set(np.zeros(g.n_slots))
+        got.append(tuple(int(c) for c in g.advection_check_adaptation(rho, 0.025 / R)))
+        assert L.dccrgx_last_error() == before
+        g.close()
+    print("counts per view", got)
+    assert got == expected
+    assert got == PARENT_COUNTS  # recorded from the library before the driver moved out of the ABI file

@@ -406,6 +406,21 @@ def w_view(k, refetch):
     return w
 
 
+def w_view_then(k, then):
+    """The write through the pointer, then a structural change: until it the
+    consumers follow the write (the field is external: no cache is built or
+    believed), after it the pointer is void and the caches are kept again."""
+    def w(g, f, sp, st):
+        dt = g.advection_max_time_step(f)
+        w_view(k, False)(g, f, sp, st)
+        if k < 4:
+            assert g.advection_max_time_step(f) < dt
+        else:
+            assert source(g, f) == 0
+        then(g, f, sp, st)
+    return w
+
+
 CASES = {
     "set": dict(writer=w_set_whole),
     "set_run": dict(writer=w_set_run),
@@ -431,6 +446,8 @@ CASES = {
     "pointer_vy_refetched": dict(writer=w_view(2, True), prepare=p_view(2)),
     "pointer_ly": dict(writer=w_view(5, False), prepare=p_view(5)),
     "pointer_ly_refetched": dict(writer=w_view(5, True), prepare=p_view(5)),
+    "pointer_vy_then_refine": dict(writer=w_view_then(2, w_refine), prepare=p_view(2), replay=True),
+    "pointer_ly_then_adapt": dict(writer=w_view_then(5, w_adapt), prepare=p_view(5), replay=True),
 }
 
 
@@ -447,16 +464,64 @@ def test_consumers_follow_the_writer(gpu, case, records):
     r = check_after_write(records=records, **CASES[case])
     if case not in NOT_AGAINST_DT:
         assert r["dt_changed"]
-    if case != "adapt":
+    if not case.endswith("adapt"):
         assert r["rho_changed"]  # (adapt: the cell is chosen for dt, no density need be near it)
     if case == "fill_geometry":
         assert r["src"] == 1
     if case == "initialize":
         assert r["dt"] == r["dt0"] and r["src"] == 1
-    if case == "adapt":
+    if case.endswith("adapt"):
         assert r["src"] == 1  # the reset lengths are the geometry's and ly is external no longer
-    if case.startswith("pointer_ly") or case in ("axpy_lx", "axpy_ly", "axpy_lz"):
+    if case in ("pointer_ly", "pointer_ly_refetched") or case in ("axpy_lx", "axpy_ly", "axpy_lz"):
         assert r["src"] == 0
+
+
+@pytest.mark.parametrize("records", [False, True], ids=["fields", "records"])
+def test_two_field_sets_with_equal_write_counts(gpu, records):
+    """Two sets of seven advection fields on one grid, added together and each
+    field written once, so that the write epochs of the two sets are equal:
+    only the field ids (and arrays) tell them apart.  Set b has other
+    velocities and one hand-edited ly.  The time step, the length check's
+    verdict and two sweeps, asked of the sets in turn, are each set's cold
+    twin's; the twins' answers differ, so a cache kept by epochs alone (set
+    a's answer for set b) would have been caught."""
+    with nbrec(records):
+        g, f, _ = build()
+        ids, cols_a = g.slot_ids(), download(g, f)
+        n = g.n_local
+        cols_b = cols_a.copy()
+        cols_b[:, 1] *= 2.0
+        cols_b[:, 2] *= -0.5
+        cols_b[int(np.argmax(cols_a[:n, 0])), 5] *= 1.25  # the cell at the top of the hump
+        sets = {}
+        for name in ("a", "b"):
+            sets[name] = [g.add_field(f"{name}_{x}", np.float64, x == "density") for x in NAMES]
+        for name, cols in (("a", cols_a), ("b", cols_b)):
+            for k in range(7):
+                sets[name][k].set(cols[:, k])
+        assert g.advection_layout()["tiles"] >= 2  # the first step already runs the tile kernels
+        order = ("a", "b", "a", "b")
+        dts = [(x, g.advection_max_time_step(sets[x])) for x in order]
+        h = 0.25 * min(dt for _, dt in dts)
+        srcs = [(x, source(g, sets[x])) for x in order]
+        dens = {"a": [], "b": []}
+        for x in order:
+            dens[x] += sweep(g, sets[x], h, steps=1)
+        dts += [(x, device_dt(g, sets[x])) for x in order]
+        srcs += [(x, source(g, sets[x])) for x in order]
+        g.close()
+    twin = {"a": cold_run(build, ids, cols_a, h), "b": cold_run(build, ids, cols_b, h)}
+    print(f"dt {dts} twins {twin['a'][0]!r} {twin['b'][0]!r} sources {srcs}")
+    # set a's answers are not set b's: a stale cache would have been seen
+    assert twin["a"][0] != twin["b"][0]
+    assert all(not np.array_equal(x, y) for x, y in zip(twin["a"][1], twin["b"][1]))
+    for x, dt in dts:
+        assert dt == twin[x][0], ("time step of set", x, dt, twin[x][0])
+    for x, src in srcs:
+        assert src == (1 if x == "a" else 0), ("length source of set", x, srcs)
+    for x in ("a", "b"):
+        for k, (got, exp) in enumerate(zip(dens[x], twin[x][1])):
+            assert np.array_equal(got, exp), ("densities of set", x, "differ from the twin's at step", k)
 
 
 def test_loaded_file_governs(gpu, tmp_path):
