@@ -1,7 +1,7 @@
 // The advection solver's host driver (tests/advection of the reference):
 // the sweep, the time step, check_for_adaptation and adapt_grid over device
 // fields, and the caches they keep (Grid::DtCache, NbRecords, LenTable,
-// BandRec).  The C ABI wrappers are in api.hip.
+// VelUniform, BandRec).  The C ABI wrappers are in api.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -122,6 +122,49 @@ const double* ensure_len_table(Grid& g, const int fids[7], bool sweep) {
 	return L.ok ? L.tab.p : nullptr;
 }
 
+// The uniform velocity components of the tile sweeps (Grid::VelUniform) for
+// the fields fids: verified as ensure_len_table verifies the lengths - one
+// pass over all slots (remote copies too) on the compute stream, one small
+// copy back - and cached on the tiles, the slot count and the three fields'
+// ids, write epochs (epoch, not local_epoch: halo receives count) and arrays.
+// While the key is found changed sweep after sweep (advection_adapt rewrites
+// the velocities every step) no pass is made and the fields are read.
+VelMask ensure_vel_uniform(Grid& g, const int fids[7], bool sweep, const double* len) {
+	Grid::VelUniform& U = g.veluni;
+	VelMask none;
+	if (adv_switch("DCCRGX_VEL_UNIFORM", 0) || g.n_slots == 0) return none;
+	if (!U.key.trackable(g, fids + 1)) return none;
+	// (the key is followed while the sweeps read the length fields too: when
+	// advection_adapt stops, both verdicts return at the same sweep)
+	if (U.keyed && U.tiles_gen == g.tiles_gen && U.n_slots == g.n_slots && U.key.same(g, fids + 1)) {
+		if (sweep) U.changed = 0;
+	} else {
+		U.key.take(g, fids + 1);
+		U.tiles_gen = g.tiles_gen;
+		U.n_slots = g.n_slots;
+		U.keyed = true;
+		U.checked = false;
+		if (sweep) ++U.changed;
+	}
+	if (!len) return none;
+	if (!U.checked) {
+		if (U.changed >= 2) return none;
+		const double* f[7];
+		for (int k = 0; k < 7; k++) f[k] = (const double*)field(g, fids[k]).data.p;
+		U.out.alloc(4);
+		k_vel_check(f, g.n_slots, U.out.p, g.s_comp);
+		uint64_t h[4] = {7, 0, 0, 0};
+		d2h_small(h, U.out.p, sizeof(h), g.s_comp);
+		U.mask = int(~h[0] & 7u);
+		std::memcpy(U.v, h + 1, sizeof(U.v));
+		U.checked = true;
+	}
+	VelMask r;
+	r.mask = U.mask;
+	std::copy(U.v, U.v + 3, r.v);
+	return r;
+}
+
 void advection_step(Grid& g, const int fids[7], double dt, int region) {
 	const double* f[7];
 	adv_fields(g, fids, f);
@@ -146,11 +189,12 @@ void advection_step(Grid& g, const int fids[7], double dt, int region) {
 		// field change, not per step)
 		const double* rec = ensure_nbrec(g, fids);
 		const double* len = ensure_len_table(g, fids, true);
+		const VelMask um = ensure_vel_uniform(g, fids, true, len);
 		DX_LAP("step.0_nbrec");
 		k_time_begin(g);
 		// tiles never straddle the inner / outer runs
-		if (s0 < g.n_inner) k_advection_tiles(f, (double*)rho.scratch.p, g, 0, dt, g.s_comp, rec, len);
-		if (s1 > g.n_inner) k_advection_tiles(f, (double*)rho.scratch.p, g, 1, dt, g.s_comp, rec, len);
+		if (s0 < g.n_inner) k_advection_tiles(f, (double*)rho.scratch.p, g, 0, dt, g.s_comp, rec, len, um.mask, um.v);
+		if (s1 > g.n_inner) k_advection_tiles(f, (double*)rho.scratch.p, g, 1, dt, g.s_comp, rec, len, um.mask, um.v);
 	} else {
 		// the bands of the check that follows computed by the sweep (with the
 		// last check's parameters), recorded per run for band_cache_ok
@@ -197,12 +241,13 @@ void advection_layout(Grid& g, uint64_t out[12]) {
 	const size_t nreg = g.tcount[0] + g.tcount[1];
 	out[8] = nreg;
 	out[9] = 512 * nreg;
-	uint64_t ext_reg = 0;
+	uint64_t ext_reg = 0, ext_reg_ax[3] = {0, 0, 0};  // (per axis of the side)
 	if (nreg) {
 		std::vector<RegTileMeta> rm(nreg);
 		d2h_small(rm.data(), g.tregmeta.p, nreg * sizeof(RegTileMeta), g.s_comp);
 		for (const auto& r : rm)
-			for (int d = 0; d < 6; d++) ext_reg += r.nst[d] >= 0 ? 64 : 0;
+			for (int d = 0; d < 6; d++) ext_reg_ax[d >> 1] += r.nst[d] >= 0 ? 64 : 0;
+		ext_reg = ext_reg_ax[0] + ext_reg_ax[1] + ext_reg_ax[2];
 	}
 	out[10] = ext_reg;
 	// 40 B per out-of-tile neighbor from the fields (density, three
@@ -214,14 +259,37 @@ void advection_layout(Grid& g, uint64_t out[12]) {
 	// last passed to an advection call): an out-of-tile neighbor is its
 	// density and one velocity (+ a level byte in the other tiles), an own
 	// cell 40 B (+ a level byte) instead of 64 B
-	uint64_t own = 64, lvl_byte = 0;
-	if (g.adv_fids_valid && ensure_len_table(g, g.adv_fids, false)) {
+	uint64_t own = 64, lvl_byte = 0, uniform = 0;
+	const double* len = g.adv_fids_valid ? ensure_len_table(g, g.adv_fids, false) : nullptr;
+	if (len) {
 		per_ext = 16;
 		lvl_byte = 1;
 		if (DCCRGX_LEN_OWN) own = 40;
+		// a uniform velocity component (ensure_vel_uniform) is not read: 8 B
+		// less per own cell and component, per regular out-of-tile neighbor
+		// across a side of its axis, and per general out-of-tile entry all of
+		// whose axis bits are uniform (it is then its density alone; an entry
+		// with another axis bit still counts the one velocity of per_ext)
+		const int um = DCCRGX_LEN_OWN && !DCCRGX_LEN_LDS ? ensure_vel_uniform(g, g.adv_fids, false, len).mask : 0;
+		if (um) {
+			Grid::VelUniform& U = g.veluni;
+			if (!U.ext_valid || U.ext_gen != g.tiles_gen) {
+				DBuf<uint64_t> d;
+				d.alloc(8);
+				const size_t ni = g.tmeta.n ? g.tcount[2] + g.tcount[3] : 0;
+				k_ext_axis_count(g.tmeta.p, ni, g.ext_pk.p, d.p, g.s_comp);
+				d2h_small(U.ext_ax, d.p, sizeof(U.ext_ax), g.s_comp);
+				U.ext_gen = g.tiles_gen;
+				U.ext_valid = true;
+			}
+			for (int a = 0; a < 3; a++)
+				if ((um >> a) & 1) uniform += 8 * n + 8 * ext_reg_ax[a];
+			for (int ax = 1; ax < 8; ax++)
+				if ((ax & ~um) == 0) uniform += 8 * U.ext_ax[ax];
+		}
 	}
 	out[11] = own * n + (12 + (own == 40 ? lvl_byte : 0)) * n_irr_cells + (per_ext + lvl_byte + 4) * ext_irr +
-	          per_ext * ext_reg + 8 * uint64_t(g.n_fine_faces) + 32 * nt;
+	          per_ext * ext_reg + 8 * uint64_t(g.n_fine_faces) + 32 * nt - uniform;
 }
 
 void advection_occupancy(Grid& g, uint64_t out[6]) {
@@ -231,9 +299,11 @@ void advection_occupancy(Grid& g, uint64_t out[6]) {
 	// the first sweep: the one it will make)
 	const bool valid = g.adv_fids_valid;
 	const bool rec = valid && ensure_nbrec(g, g.adv_fids) != nullptr;
-	const bool len = valid && ensure_len_table(g, g.adv_fids, false) != nullptr;
+	const double* tab = valid ? ensure_len_table(g, g.adv_fids, false) : nullptr;
+	const bool len = tab != nullptr;
+	const int um = valid ? ensure_vel_uniform(g, g.adv_fids, false, tab).mask : 0;
 	for (int kind = 0; kind < 2; kind++) {
-		const Grid::SweepLaunch& L = adv_sweep_launch(g, kind, rec, len);
+		const Grid::SweepLaunch& L = adv_sweep_launch(g, kind, rec, len, um);
 		int k = 0;
 		HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, L.fn, 512, L.lds));
 		out[3 * kind] = uint64_t(L.blocks_per_cu);
@@ -248,6 +318,14 @@ void advection_length_source(Grid& g, const int fids[7], int* out) {
 	adv_fields(g, fids, f);
 	ensure_tiles(g);
 	*out = ensure_len_table(g, fids, false) ? 1 : 0;
+}
+
+void advection_velocity_source(Grid& g, const int fids[7], int* mask) {
+	DX_REQUIRE(mask, "null output");
+	const double* f[7];
+	adv_fields(g, fids, f);
+	ensure_tiles(g);
+	*mask = ensure_vel_uniform(g, fids, false, ensure_len_table(g, fids, false)).mask;
 }
 
 void advection_commit(Grid& g, int df) {

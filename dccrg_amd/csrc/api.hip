@@ -2610,6 +2610,14 @@ int dccrgx_advection_length_source(dccrgx_grid* gp, const int fids[7], int* out)
 	});
 }
 
+int dccrgx_advection_velocity_source(dccrgx_grid* gp, const int fids[7], int* mask) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		advection_velocity_source(g, fids, mask);
+		return 0;
+	});
+}
+
 int dccrgx_advection_commit(dccrgx_grid* gp, int df) {
 	return guard([&] {
 		GRID_OR_FAIL(gp);

@@ -853,6 +853,28 @@ struct Grid {
 		bool ok = false;
 		int changed = 0;  // consecutive sweeps that found the key changed
 	} lentab;
+	// A uniform velocity component (ensure_vel_uniform): a component whose
+	// every slot holds one 64-bit pattern - vz of the reference's 2-D flow, all
+	// three of a uniform translation - is passed to the length-table sweeps by
+	// value instead of read as 8 B per cell and per out-of-tile neighbor.
+	// `mask` / `v` are the verdict of one device pass over all slots for the
+	// key below (tiles, slots, the three fields' ids / write epochs / arrays).
+	struct VelUniform {
+		DBuf<uint64_t> out;  // the pass' result: differs bits, slot 0's three patterns
+		FieldKey<3> key;
+		uint64_t tiles_gen = 0;
+		size_t n_slots = 0;
+		bool keyed = false;    // the key above is set
+		bool checked = false;  // `mask` and `v` belong to the key
+		int mask = 0;
+		double v[3] = {0, 0, 0};
+		int changed = 0;  // consecutive sweeps that found the key changed
+		// the general tiles' out-of-tile entries by axis-bit pattern
+		// (advection_layout), for the tiles of ext_gen
+		uint64_t ext_ax[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+		uint64_t ext_gen = 0;
+		bool ext_valid = false;
+	} veluni;
 	DBuf<uint8_t> ext_lvl;  // level of every ext_pk entry's slot (parallel to ext_pk)
 	// the fields last passed to an advection entry point (advection_layout
 	// reports the bytes of the sweep of these fields)
@@ -1151,7 +1173,8 @@ void k_advection(const double* const f[7], double* rho_out, const uint32_t* face
 // tiled advection sweep over the regular and the irregular tiles of one run
 // (run 0 inner, 1 outer: tiles never straddle the two)
 void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int run, double dt, hipStream_t s,
-                       const double* nbrec = nullptr, const double* lentab = nullptr);
+                       const double* nbrec = nullptr, const double* lentab = nullptr, int um = 0,
+                       const double uniform[3] = nullptr);
 // the per-level length table (32 rows of lx, ly, lz) for the sweep of fields
 // fids when every slot's three lengths are bitwise their level's row, checked
 // by one device pass and cached (Grid::LenTable); nullptr - the sweeps read
@@ -1194,7 +1217,28 @@ void k_tile_levels(const uint8_t* slot_lvl, const uint32_t* ext_pk, size_t n_ext
 // the launch k_advection_tiles makes (or would make, given whether the
 // neighbor records / the length table are in use) for the regular (kind 0)
 // or the other tiles (kind 1): fills and returns g.adv_launch[kind]
-const Grid::SweepLaunch& adv_sweep_launch(Grid& g, int kind, bool nbrec, bool lentab);
+// um: the mask of uniform velocity components (length-table kernels only)
+const Grid::SweepLaunch& adv_sweep_launch(Grid& g, int kind, bool nbrec, bool lentab, int um = 0);
+// The uniform velocity components of the sweep of fields fids: bit a of mask
+// set - every slot of component a (remote copies too) holds the 64-bit
+// pattern of v[a], checked by one device pass and cached (Grid::VelUniform).
+// The length-table kernels then take the component from a kernel argument.
+// Mask 0 - the sweeps read the three fields - when `len` (ensure_len_table's
+// answer for the same fields) is nullptr, a velocity field is external,
+// DCCRGX_VEL_UNIFORM=0, or the key was found changed at two sweeps in a row
+// (the velocities are rewritten every step: no pass until a sweep finds the
+// key unchanged).  sweep: the call precedes a sweep
+struct VelMask {
+	int mask = 0;
+	double v[3] = {0, 0, 0};
+};
+VelMask ensure_vel_uniform(Grid& g, const int fids[7], bool sweep, const double* len);
+// out[0]: bit a set when component a differs from slot 0's pattern in some
+// slot; out[1..3]: slot 0's three patterns
+void k_vel_check(const double* const f[7], size_t n, uint64_t* out, hipStream_t s);
+// cnt[ax], ax = 0..7: the general tiles' out-of-tile neighbor entries whose
+// ext_pk axis bits are ax (tmeta: ntiles records of 8 x u32)
+void k_ext_axis_count(const uint32_t* tmeta, size_t ntiles, const uint32_t* ext_pk, uint64_t* cnt, hipStream_t s);
 // the neighbor records for the sweep of fields fids (rho vx vy vz lx ly lz),
 // rebuilt when stale; nullptr when a velocity / length field is external
 // (or DCCRGX_NBREC=0): the sweeps then read the fields (advection.hip)

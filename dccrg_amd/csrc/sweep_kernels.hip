@@ -722,23 +722,51 @@ __device__ __forceinline__ uint32_t nb_one_row(uint32_t a) { return a == 2 ? 5u 
 // launched with, three blocks per CU (DCCRGX_REG_BLOCKS;
 // profiles/len_lds_ab.md).  DCCRGX_LEN_LDS=1 or DCCRGX_LEN_OWN=0 keep the
 // seven rows, staged from the table, and two blocks.
-template <int MINW, bool REC, bool LEN>
+//
+// UM (ensure_vel_uniform verified it): bit a set - velocity component a holds
+// one 64-bit pattern in every slot, uv.v[a].  Such a component is neither
+// loaded nor staged: shd keeps the density and the other components' rows
+// (vel_row), the out-of-tile rows are six density rows and two velocity rows
+// per other axis, and every operand that was the component - the own cell's,
+// a neighbor's, a boundary face's two - is uv.v[a], the same bits, so the
+// densities are bitwise the UM = 0 kernel's.  No arithmetic is skipped.
+struct AdvUV {
+	double v[3];
+};
+// LDS row of velocity component a when the components of mask um have none
+__host__ __device__ constexpr uint32_t vel_row(int um, uint32_t a) {
+	return 1u + a - uint32_t(__builtin_popcount(unsigned(um) & ((1u << a) - 1u)));
+}
+// the k-th axis (ascending) that is not in mask um
+__host__ __device__ constexpr uint32_t vel_live_axis(int um, uint32_t k) {
+	uint32_t a = 0;
+	for (; a < 3; a++) {
+		if ((um >> a) & 1) continue;
+		if (k == 0) break;
+		k--;
+	}
+	return a;
+}
+
+template <int MINW, bool REC, bool LEN, int UM = 0>
 __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs P, double* __restrict__ rho_out,
                                                                          const RegTileMeta* __restrict__ meta,
                                                                          uint32_t ntiles, double dt,
                                                                          const double* __restrict__ R, size_t nrec,
-                                                                         const double* __restrict__ LT) {
+                                                                         const double* __restrict__ LT, AdvUV uv) {
 #pragma clang fp contract(off)
 	static_assert(!(REC && LEN), "the length table is for the default kernels only");
 	constexpr bool LOWN = LEN && DCCRGX_LEN_OWN;
 	constexpr bool LREG = LOWN && !DCCRGX_LEN_LDS;  // the lengths stay in registers
+	static_assert(UM == 0 || (LREG && UM > 0 && UM < 8), "uniform components: the register-length kernel only");
+	constexpr int NV = 3 - __builtin_popcount(unsigned(UM));  // velocity components with a row
 	// rows rho, vx, vy, vz, lx, ly, lz; columns 0..511 the tile's own cells,
 	// 512 + 64 d + (face cell) the out-of-tile neighbor across side d (only
 	// rows rho, lx, ly, lz and the velocity along d's axis are filled), so
 	// every face reads its neighbor through one LDS index, whichever side.
 	// LREG: no length rows, every length a face reads is the tile's tl[]
 	constexpr uint32_t W = 512 + 6 * 64;
-	constexpr int NROW = LREG ? 4 : 7;
+	constexpr int NROW = LREG ? 1 + NV : 7;
 	__shared__ double shd[NROW][W];
 	__shared__ double shg[3][512];  // flux through each cell's +x, +y, +z face
 	__shared__ double shm[3][64];   // flux through the tile's -x, -y, -z boundary faces
@@ -776,6 +804,18 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 	const double* __restrict__ vz = P.p[6];
 	// LDS row of value `val` (0 rho, 1 lx, 2 ly, 3 lz, 4 velocity along a)
 	auto vrow = [](uint32_t val, uint32_t a) -> uint32_t { return val == 0 ? 0u : (val == 4 ? 1u + a : val + 3u); };
+	// LEN: the out-of-tile rows (side, value 0 rho | 4 the velocity along the
+	// side's axis) as the waves enumerate them, side and value wave-uniform.
+	// UM = 0: 12 rows, (side, value) interleaved; else the six density rows,
+	// then two velocity rows per axis that is not uniform
+	constexpr uint32_t ext_rows = UM == 0 ? 12u : 6u + 2u * uint32_t(NV);
+	auto ext_side = [](uint32_t row) -> uint32_t {
+		if (UM == 0) return row >> 1;
+		if (row < 6u) return row;
+		const uint32_t k = row - 6u;
+		return 2u * ((k >> 1) == 0 ? vel_live_axis(UM, 0) : vel_live_axis(UM, 1)) + (k & 1u);
+	};
+	auto ext_val = [](uint32_t row) -> uint32_t { return UM == 0 ? 4u * (row & 1u) : (row < 6u ? 0u : 4u); };
 	// a register set: a tile being loaded
 	struct RegSet {
 		double c[7], e[4];
@@ -792,8 +832,10 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 	auto load = [&](const RM& mt, RegSet& r) {
 		const uint32_t ts = mt.ts;
 		const uint32_t o = (ts + tid) << 3;
-		r.c[0] = ldo(rho, o); r.c[1] = ldo(vx, o); r.c[2] = ldo(vy, o);
-		r.c[3] = ldo(vz, o);
+		r.c[0] = ldo(rho, o);
+		if (!(UM & 1)) r.c[1] = ldo(vx, o);
+		if (!(UM & 2)) r.c[2] = ldo(vy, o);
+		if (!(UM & 4)) r.c[3] = ldo(vz, o);
 		if (!LOWN) {
 			r.c[4] = ldo(lx, o); r.c[5] = ldo(ly, o);
 			r.c[6] = ldo(lz, o);
@@ -804,9 +846,9 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 			r.e[i] = 0;
 			// LEN: 12 rows (side, 0 rho | 1 the velocity along the side's axis)
 			if (LEN && i >= 2) continue;
-			if (row >= (REC ? 24u : (LEN ? 12u : 30u))) continue;
-			const uint32_t d = REC ? row >> 2 : (LEN ? row >> 1 : row / 5u);
-			const uint32_t val = REC ? row & 3u : (LEN ? 4u * (row & 1u) : row - 5u * d), a = d >> 1;
+			if (row >= (REC ? 24u : (LEN ? ext_rows : 30u))) continue;
+			const uint32_t d = REC ? row >> 2 : (LEN ? ext_side(row) : row / 5u);
+			const uint32_t val = REC ? row & 3u : (LEN ? ext_val(row) : row - 5u * d), a = d >> 1;
 			const int32_t st = mt.nst(d);
 			if (st < 0) continue;
 			const uint32_t u = lane & 7u, v = lane >> 3, side = (d & 1u) ? 0u : 7u;
@@ -837,15 +879,18 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 	auto stage = [&](const RegSet& r, const TL& tlv) {
 		const double (&tl)[3] = tlv.v;
 #pragma unroll
-		for (int k = 0; k < NROW; k++) shd[k][tid] = LOWN && k >= 4 ? tl[k - 4] : r.c[k];
+		for (int k = 0; k < (UM ? 4 : NROW); k++) {
+			if (UM == 0) shd[k][tid] = LOWN && k >= 4 ? tl[k - 4] : r.c[k];
+			else if (k == 0 || !((UM >> (k - 1)) & 1)) shd[k == 0 ? 0u : vel_row(UM, uint32_t(k - 1))][tid] = r.c[k];
+		}
 #pragma unroll
 		for (int i = 0; i < 4; i++) {
 			const uint32_t row = w + 8u * uint32_t(i);
 			if (LEN) {
-				if (i < 2 && row < 12u) {
-					const uint32_t d = row >> 1, col = 512u + 64u * d + lane;
-					if (row & 1u) {
-						shd[1u + (d >> 1)][col] = r.e[i];
+				if (i < 2 && row < ext_rows) {
+					const uint32_t d = ext_side(row), col = 512u + 64u * d + lane;
+					if (ext_val(row)) {
+						shd[vel_row(UM, d >> 1)][col] = r.e[i];
 					} else {
 						shd[0][col] = r.e[i];
 						if (!LREG) {
@@ -870,11 +915,13 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 	auto lrow = [&](const TL& tl, int k, uint32_t i) -> double {
 		return LREG && k >= 4 ? tl.v[k - 4] : shd[k % NROW][i];
 	};
+	// velocity component a of LDS column i (a uniform component has no row)
+	auto vel = [&](uint32_t a, uint32_t i) -> double { return ((UM >> a) & 1) ? uv.v[a] : shd[vel_row(UM, a)][i]; };
 	// the staged tile tc from LDS
 	auto compute = [&](const RM& mc, const TL& tl) {
 		const uint32_t ts = mc.ts;
 		const double cd = shd[0][tid], clx = lrow(tl, 4, tid), cly = lrow(tl, 5, tid), clz = lrow(tl, 6, tid);
-		const double cva[3] = {shd[1][tid], shd[2][tid], shd[3][tid]};
+		const double cva[3] = {vel(0, tid), vel(1, tid), vel(2, tid)};
 		// pass 1: the +x, +y, +z face of every cell, once per face, branch-free
 		// (a missing face beyond a non-periodic boundary evaluates zeros and
 		// is masked by a select)
@@ -882,7 +929,7 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 		for (int a = 0; a < 3; a++) {
 			const uint32_t li = lp[a];
 			const double g = adv_face_g(a, cd, clx, cly, clz, cva[a],
-			                            AdvNb{shd[0][li], lrow(tl, 4, li), lrow(tl, 5, li), lrow(tl, 6, li), shd[1 + a][li]}, dt);
+			                            AdvNb{shd[0][li], lrow(tl, 4, li), lrow(tl, 5, li), lrow(tl, 6, li), vel(a, li)}, dt);
 			const bool has = l[a] < 7 || mc.nst(2 * a + 1) >= 0;
 			shg[a][tid] = has ? g : 0.0;
 		}
@@ -890,12 +937,13 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 		// waves 0..2, wave-uniform
 		if (w < 3 && mc.nst(2 * w) >= 0) {
 			const uint32_t k = 512u + 64u * (2u * w) + lane;
-			const AdvNb self{shd[0][bcell], lrow(tl, 4, bcell), lrow(tl, 5, bcell), lrow(tl, 6, bcell), shd[1 + w][bcell]};
+			const double sv = UM == 0 ? shd[1 + w][bcell] : (w == 0 ? vel(0, bcell) : (w == 1 ? vel(1, bcell) : vel(2, bcell)));
+			const AdvNb self{shd[0][bcell], lrow(tl, 4, bcell), lrow(tl, 5, bcell), lrow(tl, 6, bcell), sv};
 			const double kx = lrow(tl, 4, k), ky = lrow(tl, 5, k), kz = lrow(tl, 6, k);
 			double gmv;
-			if (w == 0) gmv = adv_face_g(0, shd[0][k], kx, ky, kz, shd[1][k], self, dt);
-			else if (w == 1) gmv = adv_face_g(1, shd[0][k], kx, ky, kz, shd[2][k], self, dt);
-			else gmv = adv_face_g(2, shd[0][k], kx, ky, kz, shd[3][k], self, dt);
+			if (w == 0) gmv = adv_face_g(0, shd[0][k], kx, ky, kz, vel(0, k), self, dt);
+			else if (w == 1) gmv = adv_face_g(1, shd[0][k], kx, ky, kz, vel(1, k), self, dt);
+			else gmv = adv_face_g(2, shd[0][k], kx, ky, kz, vel(2, k), self, dt);
 			shm[w][lane] = gmv;
 		}
 		__syncthreads();
@@ -1179,18 +1227,21 @@ struct TileMeta {
 // per-tile addresses are recomputed per tile (`ti`).  The same length bits
 // reach the same operands, so the densities are bitwise the fields'.
 // DCCRGX_LEN_LDS_GEN=1 or DCCRGX_LEN_OWN=0 keep the seven rows and two blocks.
-template <int MINW, bool REC, bool ONCE, bool LEN>
+template <int MINW, bool REC, bool ONCE, bool LEN, int UM = 0>
 __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
     AdvPtrs P, double* __restrict__ rho_out, const uint32_t* __restrict__ tell, uint32_t tplane,
     const uint32_t* __restrict__ ext, const uint32_t* __restrict__ tfine, const TileMeta* __restrict__ meta,
     uint32_t ntiles, uint32_t ecap, double dt, const double* __restrict__ R, size_t nrec,
-    const uint8_t* __restrict__ slvl, const uint8_t* __restrict__ extl, const double* __restrict__ LT) {
+    const uint8_t* __restrict__ slvl, const uint8_t* __restrict__ extl, const double* __restrict__ LT, AdvUV uv) {
 #pragma clang fp contract(off)
 	static_assert(!(LEN && (REC || ONCE)), "the length table is for the default kernels only");
 	constexpr bool LOWN = LEN && DCCRGX_LEN_OWN;
 	constexpr bool LLVL = LOWN && !DCCRGX_LEN_LDS_GEN;  // no length rows: a level byte per column
+	static_assert(UM == 0 || (LLVL && UM > 0 && UM < 8), "uniform components: the level-row kernel only");
 	constexpr uint32_t T = 512;
-	constexpr uint32_t NROW = LLVL ? 4 : 7;
+	// UM (see advection_regular_pp_kernel): a uniform component has no row
+	// (the launch still sizes the LDS for four, adv_tiles_lds)
+	constexpr uint32_t NROW = LLVL ? 4u - uint32_t(__builtin_popcount(unsigned(UM))) : 7;
 	// [NROW][T + ecap] doubles (rho vx vy vz lx ly lz); ONCE: 3 x T doubles of
 	// +a face fluxes; 2 x T u32 finer-face pairs; ONCE: 3 x T flags; LEN: 96
 	// doubles, the per-level lengths; LLVL: T + ecap level bytes
@@ -1228,7 +1279,10 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 	if (LEN && tid < 96u) lt[tid] = LT[tid];  // (read after the first tile's first barrier)
 	auto load7 = [&](uint32_t slot, double (&v)[7]) {
 		const uint32_t o = slot << 3;
-		v[0] = ldo(rho, o); v[1] = ldo(vx, o); v[2] = ldo(vy, o); v[3] = ldo(vz, o);
+		v[0] = ldo(rho, o);
+		if (!(UM & 1)) v[1] = ldo(vx, o);
+		if (!(UM & 2)) v[2] = ldo(vy, o);
+		if (!(UM & 4)) v[3] = ldo(vz, o);
 		if (LOWN) {
 			lvc = __builtin_nontemporal_load(slvl + slot);
 			return;
@@ -1246,9 +1300,9 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 		const uint32_t sl = q & 0x1fffffffu, o = sl << 3, ax = q >> 29;
 		v[0] = ldo(rho, o);
 		if (LEN) {
-			v[1] = (ax & 1u) ? ldo(vx, o) : 0.0;
-			v[2] = (ax & 2u) ? ldo(vy, o) : 0.0;
-			v[3] = (ax & 4u) ? ldo(vz, o) : 0.0;
+			if (!(UM & 1)) v[1] = (ax & 1u) ? ldo(vx, o) : 0.0;
+			if (!(UM & 2)) v[2] = (ax & 2u) ? ldo(vy, o) : 0.0;
+			if (!(UM & 4)) v[3] = (ax & 4u) ? ldo(vz, o) : 0.0;
 			return;
 		}
 		if (REC && (ax == 1u || ax == 2u || ax == 4u)) {
@@ -1305,6 +1359,13 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 			fq[1] = q.y;
 		}
 	};
+	// UM: a register set into LDS column col, the density and the live components
+	auto stage = [&](uint32_t col, const double (&v)[7]) {
+		shd[col] = v[0];
+#pragma unroll
+		for (uint32_t a = 0; a < 3; a++)
+			if (!((UM >> a) & 1)) shd[vel_row(UM, a) * W + col] = v[1 + a];
+	};
 	GM cur = unpack(tile_record_word(meta, t, lane));
 	uint32_t tn = tk.next(t);
 	load(cur);
@@ -1315,14 +1376,22 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 		__syncthreads();  // the previous tile's faces have been read from LDS
 		if (tid < n) {
 			if (LOWN && !LLVL) lengths(lvc, c);
+			if (UM) {
+				stage(ti, c);
+			} else {
 #pragma unroll
-			for (uint32_t k = 0; k < NROW; k++) shd[k * W + ti] = c[k];
+				for (uint32_t k = 0; k < NROW; k++) shd[k * W + ti] = c[k];
+			}
 			if (LLVL) shl[ti] = uint8_t(lvc);
 		}
 		if (tid < ne) {
 			if (LEN && !LLVL) lengths(lva, xa);
+			if (UM) {
+				stage(T + ti, xa);
+			} else {
 #pragma unroll
-			for (uint32_t k = 0; k < NROW; k++) shd[k * W + T + ti] = xa[k];
+				for (uint32_t k = 0; k < NROW; k++) shd[k * W + T + ti] = xa[k];
+			}
 			if (LLVL) shl[T + ti] = uint8_t(lva);
 		}
 		if (tid + T < ne) {
@@ -1333,8 +1402,12 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 			} else if (LEN) {
 				lengths(lvb, xb);
 			}
+			if (UM) {
+				stage(2 * T + ti, xb);
+			} else {
 #pragma unroll
-			for (uint32_t k = 0; k < NROW; k++) shd[k * W + 2 * T + ti] = xb[k];
+				for (uint32_t k = 0; k < NROW; k++) shd[k * W + 2 * T + ti] = xb[k];
+			}
 		}
 		if (tid < nf) {
 			shf[2 * ti] = fq[0];
@@ -1356,9 +1429,9 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 		double cd = 0, cvx = 0, cvy = 0, cvz = 0, clx = 1, cly = 1, clz = 1;
 		if (own) {
 			cd = shd[ti];
-			cvx = shd[W + ti];
-			cvy = shd[2 * W + ti];
-			cvz = shd[3 * W + ti];
+			cvx = (UM & 1) ? uv.v[0] : shd[vel_row(UM, 0) * W + ti];
+			cvy = (UM & 2) ? uv.v[1] : shd[vel_row(UM, 1) * W + ti];
+			cvz = (UM & 4) ? uv.v[2] : shd[vel_row(UM, 2) * W + ti];
 			if (LLVL) {
 				// own lengths: the table row of the cell's level byte, kept in
 				// registers across the compute phase
@@ -1374,7 +1447,8 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 			if (LLVL) {
 				// a neighbor's lengths: the table row of its column's level byte
 				const uint32_t k = 3u * (uint32_t(shl[li]) & 31u);
-				return AdvNb{shd[li], lt[k], lt[k + 1], lt[k + 2], shd[(1 + (d >> 1)) * W + li]};
+				const uint32_t a = uint32_t(d >> 1);
+				return AdvNb{shd[li], lt[k], lt[k + 1], lt[k + 2], ((UM >> a) & 1) ? uv.v[a] : shd[vel_row(UM, a) * W + li]};
 			}
 			return AdvNb{shd[li], shd[(4 % NROW) * W + li], shd[(5 % NROW) * W + li], shd[(6 % NROW) * W + li],
 			             shd[(1 + (d >> 1)) * W + li]};
@@ -2157,14 +2231,36 @@ static size_t adv_tiles_lds(uint32_t ecap, bool once, bool len) {
 	       (lvl_row ? (W + 7) / 8 * 8 : 0);
 }
 
-const Grid::SweepLaunch& adv_sweep_launch(Grid& g, int kind, bool nbrec, bool lentab) {
+// The length-table kernels' instantiation for the mask of uniform velocity
+// components (ensure_vel_uniform): f(std::integral_constant<int, UM>)
+template <class F>
+static auto with_vel_mask(int um, F&& f) {
+	switch (um & 7) {
+		case 1: return f(std::integral_constant<int, 1>{});
+		case 2: return f(std::integral_constant<int, 2>{});
+		case 3: return f(std::integral_constant<int, 3>{});
+		case 4: return f(std::integral_constant<int, 4>{});
+		case 5: return f(std::integral_constant<int, 5>{});
+		case 6: return f(std::integral_constant<int, 6>{});
+		case 7: return f(std::integral_constant<int, 7>{});
+		default: return f(std::integral_constant<int, 0>{});
+	}
+}
+// the masks exist for the register / level-row forms only
+constexpr bool kRegMasks = DCCRGX_LEN_OWN && !DCCRGX_LEN_LDS, kGenMasks = DCCRGX_LEN_OWN && !DCCRGX_LEN_LDS_GEN;
+
+const Grid::SweepLaunch& adv_sweep_launch(Grid& g, int kind, bool nbrec, bool lentab, int um) {
 	const void* fn;
 	size_t lds_min = 0;
 	int cap = 2;
 	bool table;  // a length-table kernel (the others keep their fixed two blocks per CU)
 	if (kind == 0) {
 		if (nbrec) fn = reinterpret_cast<const void*>(advection_regular_pp_kernel<4, true, false>);
-		else if (lentab) fn = reinterpret_cast<const void*>(advection_regular_pp_kernel<kRegWaves, false, true>);
+		else if (lentab)
+			fn = with_vel_mask(kRegMasks ? um : 0, [](auto M) {
+				return reinterpret_cast<const void*>(
+				    advection_regular_pp_kernel<kRegWaves, false, true, kRegMasks ? decltype(M)::value : 0>);
+			});
 		else fn = reinterpret_cast<const void*>(advection_regular_pp_kernel<4, false, false>);
 		table = !nbrec && lentab;
 		if (table) cap = DCCRGX_REG_BLOCKS;
@@ -2173,7 +2269,11 @@ const Grid::SweepLaunch& adv_sweep_launch(Grid& g, int kind, bool nbrec, bool le
 		if (nbrec && once) fn = reinterpret_cast<const void*>(advection_tiles_pp_kernel<4, true, true, false>);
 		else if (nbrec) fn = reinterpret_cast<const void*>(advection_tiles_pp_kernel<4, true, false, false>);
 		else if (once) fn = reinterpret_cast<const void*>(advection_tiles_pp_kernel<4, false, true, false>);
-		else if (len) fn = reinterpret_cast<const void*>(advection_tiles_pp_kernel<kGenWaves, false, false, true>);
+		else if (len)
+			fn = with_vel_mask(kGenMasks ? um : 0, [](auto M) {
+				return reinterpret_cast<const void*>(
+				    advection_tiles_pp_kernel<kGenWaves, false, false, true, kGenMasks ? decltype(M)::value : 0>);
+			});
 		else fn = reinterpret_cast<const void*>(advection_tiles_pp_kernel<4, false, false, false>);
 		lds_min = adv_tiles_lds(uint32_t(g.max_ext), once, len);
 		table = len;
@@ -2206,8 +2306,10 @@ const Grid::SweepLaunch& adv_sweep_launch(Grid& g, int kind, bool nbrec, bool le
 }
 
 void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int run, double dt, hipStream_t s,
-                       const double* nbrec, const double* lentab) {
+                       const double* nbrec, const double* lentab, int um, const double uniform[3]) {
 	const size_t n_reg = g.tcount[run], n_irr = g.tcount[2 + run];
+	const AdvUV uv{{uniform ? uniform[0] : 0.0, uniform ? uniform[1] : 0.0, uniform ? uniform[2] : 0.0}};
+	if (!lentab || nbrec || !uniform) um = 0;
 	const AdvPtrs P{{f[0], f[4], f[5], f[6], f[1], f[2], f[3]}};
 	if (n_irr && !g.tmeta.n) {
 		// a tile beyond the pipelined kernel's capacities: the whole run untiled
@@ -2236,17 +2338,19 @@ void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int r
 			const unsigned nblk = unsigned(std::min<size_t>(size_t(256) * 3, (n_reg + 7) / 8 * 8));
 			advection_regular3_kernel<6><<<nblk, 512, 0, s>>>(P, rho_out, meta, uint32_t(n_reg), dt);
 		} else {
-			const Grid::SweepLaunch& L = adv_sweep_launch(g, 0, nbrec != nullptr, lentab != nullptr);
+			const Grid::SweepLaunch& L = adv_sweep_launch(g, 0, nbrec != nullptr, lentab != nullptr, um);
 			const unsigned nblk = unsigned(std::min<size_t>(size_t(256) * L.blocks_per_cu, (n_reg + 7) / 8 * 8));
 			if (nbrec)
 				advection_regular_pp_kernel<4, true, false><<<nblk, 512, L.lds, s>>>(P, rho_out, meta, uint32_t(n_reg),
-				                                                                     dt, nbrec, g.n_slots, nullptr);
+				                                                                     dt, nbrec, g.n_slots, nullptr, uv);
 			else if (lentab)
-				advection_regular_pp_kernel<kRegWaves, false, true><<<nblk, 512, L.lds, s>>>(
-				    P, rho_out, meta, uint32_t(n_reg), dt, nullptr, 0, lentab);
+				with_vel_mask(kRegMasks ? um : 0, [&](auto M) {
+					advection_regular_pp_kernel<kRegWaves, false, true, kRegMasks ? decltype(M)::value : 0>
+					    <<<nblk, 512, L.lds, s>>>(P, rho_out, meta, uint32_t(n_reg), dt, nullptr, 0, lentab, uv);
+				});
 			else
 				advection_regular_pp_kernel<4, false, false><<<nblk, 512, L.lds, s>>>(P, rho_out, meta, uint32_t(n_reg),
-				                                                                      dt, nullptr, 0, nullptr);
+				                                                                      dt, nullptr, 0, nullptr, uv);
 		}
 		HIP_CHECK(hipGetLastError());
 	}
@@ -2255,30 +2359,32 @@ void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int r
 		const uint32_t ecap = uint32_t(g.max_ext);
 		const bool once = adv_face_once();
 		const bool len = lentab && !nbrec && !once;  // the length table: the default kernel only
-		const Grid::SweepLaunch& L = adv_sweep_launch(g, 1, nbrec != nullptr, lentab != nullptr);
+		const Grid::SweepLaunch& L = adv_sweep_launch(g, 1, nbrec != nullptr, lentab != nullptr, um);
 		const size_t lds = L.lds;
 		const unsigned nblk = unsigned(std::min<size_t>(size_t(256) * L.blocks_per_cu, (n_irr + 7) / 8 * 8));
 		const uint32_t tp = uint32_t(g.n_local + 1);
 		if (nbrec && once)
 			advection_tiles_pp_kernel<4, true, true, false><<<nblk, 512, lds, s>>>(
 			    P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt, nbrec, g.n_slots, nullptr,
-			    nullptr, nullptr);
+			    nullptr, nullptr, uv);
 		else if (nbrec)
 			advection_tiles_pp_kernel<4, true, false, false><<<nblk, 512, lds, s>>>(
 			    P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt, nbrec, g.n_slots, nullptr,
-			    nullptr, nullptr);
+			    nullptr, nullptr, uv);
 		else if (once)
 			advection_tiles_pp_kernel<4, false, true, false><<<nblk, 512, lds, s>>>(
 			    P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt, nullptr, 0, nullptr,
-			    nullptr, nullptr);
+			    nullptr, nullptr, uv);
 		else if (len)
-			advection_tiles_pp_kernel<kGenWaves, false, false, true><<<nblk, 512, lds, s>>>(
-			    P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt, nullptr, 0, g.slot_lvl.p,
-			    g.ext_lvl.p, lentab);
+			with_vel_mask(kGenMasks ? um : 0, [&](auto M) {
+				advection_tiles_pp_kernel<kGenWaves, false, false, true, kGenMasks ? decltype(M)::value : 0>
+				    <<<nblk, 512, lds, s>>>(P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt,
+				                            nullptr, 0, g.slot_lvl.p, g.ext_lvl.p, lentab, uv);
+			});
 		else
 			advection_tiles_pp_kernel<4, false, false, false><<<nblk, 512, lds, s>>>(
 			    P, rho_out, g.tell.p, tp, g.ext_pk.p, g.tfine.p, meta, uint32_t(n_irr), ecap, dt, nullptr, 0, nullptr,
-			    nullptr, nullptr);
+			    nullptr, nullptr, uv);
 		HIP_CHECK(hipGetLastError());
 	}
 }
@@ -2303,6 +2409,56 @@ void k_len_check(const double* const f[7], const uint8_t* slot_lvl, size_t n, co
 	HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), s));
 	if (!n) return;
 	len_check_kernel<<<grid_for(n, 256, 256u * 16u), 256, 0, s>>>(f[4], f[5], f[6], slot_lvl, n, tab, flag);
+	HIP_CHECK(hipGetLastError());
+}
+
+// ensure_vel_uniform's check: out[0] bit a = 1 when some slot's velocity
+// component a is not the 64-bit pattern of slot 0; out[1 + a] that pattern
+__global__ void vel_check_kernel(const uint64_t* __restrict__ vx, const uint64_t* __restrict__ vy,
+                                 const uint64_t* __restrict__ vz, size_t n, uint64_t* __restrict__ out) {
+	const uint64_t x0 = vx[0], y0 = vy[0], z0 = vz[0];
+	unsigned diff = 0;
+	for (size_t s = blockIdx.x * size_t(blockDim.x) + threadIdx.x; s < n; s += size_t(gridDim.x) * blockDim.x)
+		diff |= (vx[s] != x0 ? 1u : 0u) | (vy[s] != y0 ? 2u : 0u) | (vz[s] != z0 ? 4u : 0u);
+	if (diff) atomicOr(reinterpret_cast<unsigned long long*>(out), (unsigned long long)diff);
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		out[1] = x0;
+		out[2] = y0;
+		out[3] = z0;
+	}
+}
+
+void k_vel_check(const double* const f[7], size_t n, uint64_t* out, hipStream_t s) {
+	HIP_CHECK(hipMemsetAsync(out, 0, 4 * sizeof(uint64_t), s));
+	if (!n) return;
+	vel_check_kernel<<<grid_for(n, 256, 256u * 16u), 256, 0, s>>>(
+	    reinterpret_cast<const uint64_t*>(f[1]), reinterpret_cast<const uint64_t*>(f[2]),
+	    reinterpret_cast<const uint64_t*>(f[3]), n, out);
+	HIP_CHECK(hipGetLastError());
+}
+
+// the out-of-tile neighbor entries of the general tiles (ntiles records of
+// 8 x u32: word 2 the first entry, word 3 their count) by axis-bit pattern:
+// cnt[ax] entries of ext_pk hold the bits ax
+__global__ __launch_bounds__(256) void ext_axis_count_kernel(const uint32_t* __restrict__ tmeta, size_t ntiles,
+                                                             const uint32_t* __restrict__ ext_pk,
+                                                             unsigned long long* __restrict__ cnt) {
+	__shared__ unsigned sh[8];
+	if (threadIdx.x < 8) sh[threadIdx.x] = 0;
+	__syncthreads();
+	for (size_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+		const uint32_t e0 = tmeta[8 * t + 2], ne = tmeta[8 * t + 3];
+		for (uint32_t k = threadIdx.x; k < ne; k += blockDim.x) atomicAdd(&sh[ext_pk[e0 + k] >> 29], 1u);
+	}
+	__syncthreads();
+	if (threadIdx.x < 8 && sh[threadIdx.x]) atomicAdd(cnt + threadIdx.x, (unsigned long long)sh[threadIdx.x]);
+}
+
+void k_ext_axis_count(const uint32_t* tmeta, size_t ntiles, const uint32_t* ext_pk, uint64_t* cnt, hipStream_t s) {
+	HIP_CHECK(hipMemsetAsync(cnt, 0, 8 * sizeof(uint64_t), s));
+	if (!ntiles) return;
+	ext_axis_count_kernel<<<unsigned(std::min<size_t>(ntiles, 1024)), 256, 0, s>>>(
+	    tmeta, ntiles, ext_pk, reinterpret_cast<unsigned long long*>(cnt));
 	HIP_CHECK(hipGetLastError());
 }
 

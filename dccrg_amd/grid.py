@@ -1241,6 +1241,15 @@ class Dccrg:
         check(lib().dccrgx_advection_length_source(self.h, self._fids(fields), C.byref(v)))
         return v.value
 
+    def advection_velocity_source(self, fields):
+        """The mask of velocity components (bit 0 vx, 1 vy, 2 vz) that hold one
+        bit pattern in every slot and that the tile sweeps of `fields` take
+        from a kernel argument; 0 when they read the three fields (see
+        include/dccrgx.h)."""
+        v = C.c_int()
+        check(lib().dccrgx_advection_velocity_source(self.h, self._fids(fields), C.byref(v)))
+        return v.value
+
     def advection_layout(self):
         """Tile layout of the advection sweep and its algorithmic HBM bytes per
         sweep over all local cells (see include/dccrgx.h)."""

@@ -893,7 +893,13 @@ int dccrgx_advection_adapt(dccrgx_grid* g, const int fields[7], uint64_t out[2])
  * per-level table (dccrgx_advection_length_source), [11] counts 40 B per own
  * cell (41 B in an irregular tile: its level byte) and 16 B per out-of-tile
  * neighbor (density and the velocity along the face; + its level byte in an
- * irregular tile); [6] and [7] stay SURVEY's definition.
+ * irregular tile).  When that sweep also takes a velocity component from a
+ * kernel argument (dccrgx_advection_velocity_source), [11] counts per uniform
+ * component 8 B less per own cell and per out-of-tile neighbor of a regular
+ * tile across a side of that axis, and 8 B less per out-of-tile neighbor
+ * entry of an irregular tile every axis of whose faces is uniform (counted on
+ * the device from the entries' axis bits).  [6] and [7] stay SURVEY's
+ * definition.
  * No reference counterpart (roofline introspection). */
 int dccrgx_advection_layout(dccrgx_grid* g, uint64_t out[12]);
 
@@ -917,6 +923,19 @@ int dccrgx_advection_occupancy(dccrgx_grid* g, uint64_t out[6]);
  * block is held, or DCCRGX_LEN_TABLE=0).  The densities are bitwise the same
  * either way.  No reference counterpart. */
 int dccrgx_advection_length_source(dccrgx_grid* g, const int fids[7], int* out);
+
+/* Which velocity components the tile sweeps of fields fids take from a kernel
+ * argument instead of reading them: bit a of *mask (0 vx, 1 vy, 2 vz) is set
+ * when every slot of that field, remote copies included, holds one 64-bit
+ * pattern (-0.0 among +0.0 is not uniform, equal NaN patterns are), found by
+ * one device pass and cached until the tiles or one of the three fields
+ * change.  0: the sweeps read the three fields - a component differs
+ * somewhere, a velocity field's device pointer is out, the sweeps read the
+ * length fields (dccrgx_advection_length_source is 0), the velocities were
+ * found rewritten before two sweeps in a row (no pass is made then until a
+ * sweep finds them unwritten), or DCCRGX_VEL_UNIFORM=0.  The densities are
+ * bitwise the same either way.  No reference counterpart. */
+int dccrgx_advection_velocity_source(dccrgx_grid* g, const int fids[7], int* mask);
 
 /* ---- Poisson solver (tests/poisson/poisson_solve.hpp:156-1056) ----------
  * dccrgx_poisson_cache = Poisson_Solve::cache_system_info (827-971): local
