@@ -1,5 +1,6 @@
-// Host driver functions shared by grid.hip (halo, refinement, migration,
-// sweeps) and api.hip (the C ABI).
+// Host driver functions: what api.hip (the C ABI) calls and what the drivers'
+// files (grid.hip, mesh.hip, advection.hip, particles.hip, poisson.hip, ...)
+// share.
 #pragma once
 
 #include "dccrgx_internal.hpp"
@@ -46,6 +47,47 @@ void migration_place_peer(Grid& g, int peer, const uint8_t* buf, size_t bytes);
 std::vector<uint64_t> cells_by_criteria(Grid& g, const int32_t* crit, size_t nc, bool exact, int hood);
 int64_t host_slot_of(Grid& g, uint64_t id);
 bool gol_slab_plan(Grid& g, std::vector<GolBox>& inner, std::vector<GolBox>& outer);
+// grid.hip: what the setters, dccrgx_initialize and the grid-file loader
+// share: the limits of the refinement level and of the neighborhood length,
+// and the first build of the mesh
+int max_possible_level(const uint64_t len[3]);
+unsigned max_hood_length();
+void init_impl(Grid& g);
+// grid.hip: dccrgx_gol_step, one step of the uniform game of life into the
+// state field's scratch
+void gol_step(Grid& g, int sf, int region);
+// gol_amr.hip: the refined game of life, one phase (0 collect, 1 spread) over
+// a region or a whole turn with its halo; the reference's aborts are raised
+void gol_amr_phase(Grid& g, int phase, int sf, int lf, int region);
+void gol_live_neighbors(Grid& g, int sf, int lf);
+// mesh.hip: dccrgx_mapping_batch, the device id math for n host ids (level[i]
+// and 15 words per id)
+void mapping_batch(Grid& g, const uint64_t* ids, size_t n, int32_t* level, uint64_t* out);
+
+// poisson.hip: the Poisson solver's driver, one function per dccrgx_poisson_*
+// entry point of dccrgx.h (the kernels: poisson_kernels.hip)
+void poisson_cache(Grid& g, int rhs, int sol, const uint64_t* solve, size_t ns, const uint64_t* skip, size_t nk);
+void poisson_solve(Grid& g, unsigned max_iterations, unsigned min_iterations, double stop_residual, double p_of_norm,
+                   double stop_after_residual_increase, bool failsafe, unsigned* iterations, double* residual);
+int poisson_field(Grid& g, const char* name);  // the id of the solver's field "poisson.<name>"
+
+// grid_file.hip: save_grid_data and load_grid_data, whole or in its three
+// steps (sizes: a variable-size field's byte count of every local cell)
+void save_grid_impl(Grid& g, const char* path, uint64_t offset, const void* header, size_t header_bytes);
+void load_grid_impl(Grid& g, const char* path, uint64_t offset, size_t header_bytes);
+void start_load_impl(Grid& g, const char* path, uint64_t offset, size_t header_bytes);
+void continue_load_impl(Grid& g, int fid, const uint64_t* sizes);
+void finish_load_impl(Grid& g);
+void grid_file_bytes_left(Grid& g, uint64_t* bytes);
+
+// field_ops.hip: the operators on fp64 cell fields, one function per entry
+// point (dccrgx_gradient, _curl, _divergence, _field_axpy,
+// _field_reduce_device); every check precedes the first write
+void field_gradient(Grid& g, int in_field, const int out_fields[3], double scale, int region);
+void field_curl(Grid& g, const int in_fields[3], const int out_fields[3], double scale, bool accumulate, int region);
+void field_divergence(Grid& g, const int in_fields[3], int out_field, double scale, bool accumulate, int region);
+void field_axpy(Grid& g, int y_field, double a, int x_field, int region);
+void field_reduce_device(Grid& g, const int* terms, int n, int by_volume, int region, int collective, double* d_out);
 
 // advection.hip: the advection solver's driver, one function per
 // dccrgx_advection_* entry point of dccrgx.h (fids: rho vx vy vz lx ly lz)
@@ -125,8 +167,29 @@ const double* stretched_device(Grid& g);
 // the same with each dimension's offset, for the Poisson cache pass and the
 // advection reset pass (Cartesian grid: c == nullptr, nothing uploaded)
 StretchedView stretched_view(Grid& g);
+// the stencil arguments of the kernels over the face table, the table built
+inline FaceStencil face_stencil(Grid& g) {
+	ensure_face(g);
+	return {g.m, g.l0, stretched_view(g), g.slot_ids.p, g.slot_lvl.p, g.face_ell.p, g.face_fine.p};
+}
 // geometry.hip: the fp64 center and / or length of every slot's cell into
 // fixed-size fp64 fields (-1: none), Cartesian or stretched
 void geometry_fill(Grid& g, const int center_fields[3], const int length_fields[3]);
+// the same on the host for n ids (NaN for an id that is no cell)
+void geometry_batch(Grid& g, const uint64_t* ids, size_t n, double* center, double* length);
+// the stretched geometry from three coordinate arrays (checked), and a
+// geometry block for the grid file alone (n == 0: none)
+void set_stretched_geometry(Grid& g, const double* const coords[3], const size_t n[3]);
+void set_geometry_block(Grid& g, const void* bytes, size_t n);
+// the geometry block of a grid file (after mapping, neighborhood length and
+// topology): its first int names the geometry.  The stretched one's block is
+// kStretchedBlockHead bytes (the id, three uint64 coordinate counts) and the
+// coordinates: stretched_block builds it, stretched_block_bytes sizes it from
+// its head (0: no valid block), stretched_block_coords reads a checked one back
+constexpr int kCartesianGeometryId = 1, kStretchedGeometryId = 2;
+constexpr size_t kStretchedBlockHead = 28;
+std::vector<uint8_t> stretched_block(const double* const coords[3], const size_t n[3]);
+size_t stretched_block_bytes(const uint8_t* head);
+void stretched_block_coords(const std::vector<uint8_t>& block, std::vector<double> c[3]);
 
 }  // namespace dccrgx

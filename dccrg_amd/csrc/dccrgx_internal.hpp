@@ -297,6 +297,23 @@ inline unsigned grid_for(size_t n, unsigned per_block, unsigned cap = 256u * 32u
 	return unsigned(g);
 }
 
+// XCD-contiguous block order: hardware block b runs on XCD b % 8, so XCD x
+// sweeps the contiguous x-th eighth of the logical blocks and the neighbor
+// rows a block gathers were fetched into the same XCD's L2 shortly before,
+// not into all eight (gridDim.x must be a multiple of 8: xcd_blocks, xcd_grid)
+__device__ __forceinline__ unsigned xcd_block() {
+	return (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+}
+// blocks of BS threads over n slots in whole rounds over the 8 XCDs
+// (xcd_block is onto); the per-slot kernels of poisson_kernels.hip and
+// field_ops.hip are launched with it
+constexpr int BS = 256;
+inline unsigned xcd_blocks(size_t n) {
+	size_t b = (n + BS - 1) / BS;
+	b = (b + 7) / 8 * 8;
+	return unsigned(b ? b : 8);
+}
+
 // A field: one SoA array over all slots.  The halo carries bytes
 // [win_off, win_off + win_len) of every element (the part a Cell_Data's
 // get_mpi_datatype describes, dccrg_get_cell_datatype.hpp:40-340); the whole
@@ -418,6 +435,18 @@ struct Restore {
 struct StretchedView {
 	const double* c = nullptr;
 	uint32_t off[3] = {0, 0, 0};
+};
+
+// what a launcher of a kernel over the face table takes from the grid
+// (face_stencil, dccrgx_grid.hpp); the launcher unpacks it at the <<<>>>, the
+// kernels' parameter lists hold the members one by one
+struct FaceStencil {
+	const MapCtx& m;
+	const double* l0;  // [3]
+	StretchedView G;   // G.c given: the stretched geometry's lengths instead of l0's
+	const uint64_t* slot_ids;
+	const uint8_t* slot_lvl;  // the level byte of every slot (ensure_face)
+	const int32_t *face_ell, *face_fine;
 };
 
 // ---- Poisson BiCG (tests/poisson/poisson_solve.hpp) ------------------------
@@ -1307,10 +1336,8 @@ void k_field_merge_parents(const FollowSet& F, const int32_t* pslot, const int32
 // the slope pass over the n refined cells `refined` (old local slot pslot[i],
 // skipped where it is none or no local slot): t_d of the nlin old arrays in,
 // and ppos[pslot[i]] = i
-void k_field_slopes(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
-                    const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine, size_t n_local,
-                    const int32_t* pslot, size_t n, const double* const* in, int nlin, double* t, int32_t* ppos,
-                    hipStream_t s);
+void k_field_slopes(const FaceStencil& F, size_t n_local, const int32_t* pslot, size_t n, const double* const* in,
+                    int nlin, double* t, int32_t* ppos, hipStream_t s);
 // rebuild step 6 for a field that follows with SUM or LINEAR: k_gather_rows
 // with the child rule where a new local slot's source is a coarser old cell
 void k_field_follow_gather(const MapCtx& m, const double* old_data, const int32_t* src, size_t n_slots, size_t n_local,
@@ -1366,35 +1393,34 @@ void k_gol_amr(int phase, GolAmrTables& T, size_t n_slots, size_t n_local, uint3
                const int* gate = nullptr);
 
 // --- launchers implemented in poisson_kernels.hip ---------------------------
-unsigned k_po_blocks(size_t n);  // blocks (= partials) of a phase launch over n slots
+// (a phase launch over n slots has xcd_blocks(n) blocks = partials)
+// cls[slot of ids[i]] = value for the ids that are local cells
+void k_po_classify(int32_t* cls, const DevMesh& M, const uint64_t* ids, size_t n, size_t n_local, int32_t value,
+                   hipStream_t s);
 void k_po_transpose(const PoArrays& a, size_t n, double* ft, hipStream_t s);
-// (G.c given: the lengths of the stretched geometry instead of l0's)
-void k_po_cache(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
-                const int32_t* cls, const int32_t* face_ell, const int32_t* face_fine, size_t n, int32_t* po_ell,
-                int32_t* po_fine, int32_t* type, const PoArrays& a, hipStream_t s);
+// (cls, every slot's classification, in place of F.slot_lvl)
+void k_po_cache(const FaceStencil& F, const int32_t* cls, size_t n, int32_t* po_ell, int32_t* po_fine, int32_t* type,
+                const PoArrays& a, hipStream_t s);
 void k_po_phase(int phase, const PoArrays& a, size_t n, const PoParams& prm, const PoScalars* st, double* part,
                 hipStream_t s);
 void k_po_reduce(int k, const double* part, unsigned nb, double* red, PoScalars* st, const PoParams& prm, int stage,
                  bool scalar, hipStream_t s);
 // all: P x k all-gathered per-rank sums, combined in rank order
 void k_po_scalar(const double* all, int P, int k, PoScalars* st, const PoParams& prm, int stage, hipStream_t s);
+
+// --- launchers implemented in field_ops.hip ---------------------------------
 // dccrgx_gradient over the local slots [s0, s1): out[d] (nullptr: not wanted)
-// = scale * the d-component of the gradient of `in` (G.c given: the stretched
-// geometry's lengths); slot_lvl: the level byte of every slot (ensure_face)
-void k_gradient(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
-                const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine, const double* in,
-                double* const out[3], double scale, size_t s0, size_t s1, hipStream_t s);
+// = scale * the d-component of the gradient of `in`
+void k_gradient(const FaceStencil& F, const double* in, double* const out[3], double scale, size_t s0, size_t s1,
+                hipStream_t s);
 // dccrgx_curl over the local slots [s0, s1): out[k] (nullptr: not wanted) = or
 // += scale * the k-component of the curl of the three fields `in`, whose
 // derivatives are k_gradient's bit for bit
-void k_curl(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
-            const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine, const double* const in[3],
-            double* const out[3], double scale, bool accumulate, size_t s0, size_t s1, hipStream_t s);
+void k_curl(const FaceStencil& F, const double* const in[3], double* const out[3], double scale, bool accumulate,
+            size_t s0, size_t s1, hipStream_t s);
 // dccrgx_divergence likewise: out = or += scale * ((D_0 in[0] + D_1 in[1]) + D_2 in[2])
-void k_divergence(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
-                  const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine,
-                  const double* const in[3], double* out, double scale, bool accumulate, size_t s0, size_t s1,
-                  hipStream_t s);
+void k_divergence(const FaceStencil& F, const double* const in[3], double* out, double scale, bool accumulate,
+                  size_t s0, size_t s1, hipStream_t s);
 // dccrgx_field_axpy: y = y + (a * x) over the slots [s0, s1)
 void k_field_axpy(double* y, double a, const double* x, size_t s0, size_t s1, hipStream_t s);
 

@@ -1,5 +1,5 @@
 // The first-derivative stencil over the face table, shared by the kernels of
-// poisson_kernels.hip (gradient, curl, divergence) and field_adapt.hip (the
+// field_ops.hip (gradient, curl, divergence) and field_adapt.hip (the
 // slopes of a limited linear prolongation): one definition, so one set of bits.
 #pragma once
 

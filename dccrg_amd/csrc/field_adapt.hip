@@ -250,22 +250,20 @@ void k_field_merge_parents(const FollowSet& F, const int32_t* pslot, const int32
 	HIP_CHECK(hipGetLastError());
 }
 
-void k_field_slopes(const MapCtx& m, const double l0[3], const StretchedView& G, const uint64_t* slot_ids,
-                    const uint8_t* slot_lvl, const int32_t* face_ell, const int32_t* face_fine, size_t n_local,
-                    const int32_t* pslot, size_t n, const double* const* in, int nlin, double* t, int32_t* ppos,
-                    hipStream_t s) {
+void k_field_slopes(const FaceStencil& S, size_t n_local, const int32_t* pslot, size_t n, const double* const* in,
+                    int nlin, double* t, int32_t* ppos, hipStream_t s) {
 	if (!n) return;
 	for (int j0 = 0; j0 < nlin; j0 += kFollowBatch) {
 		const int nb = std::min(kFollowBatch, nlin - j0);
 		SlopeFields F;
 		for (int j = 0; j < kFollowBatch; j++) F.in[j] = in[j0 + std::min(j, nb - 1)];
 		const dim3 grid(grid_for(n, FBS), unsigned(nb));
-		if (G.c)
-			field_slopes_kernel<true><<<grid, FBS, 0, s>>>(m, l0[0], l0[1], l0[2], G, slot_ids, slot_lvl, face_ell,
-			                                               face_fine, n_local, pslot, n, F, j0, t, ppos);
+		if (S.G.c)
+			field_slopes_kernel<true><<<grid, FBS, 0, s>>>(S.m, S.l0[0], S.l0[1], S.l0[2], S.G, S.slot_ids, S.slot_lvl,
+			                                               S.face_ell, S.face_fine, n_local, pslot, n, F, j0, t, ppos);
 		else
-			field_slopes_kernel<false><<<grid, FBS, 0, s>>>(m, l0[0], l0[1], l0[2], G, slot_ids, slot_lvl, face_ell,
-			                                                face_fine, n_local, pslot, n, F, j0, t, ppos);
+			field_slopes_kernel<false><<<grid, FBS, 0, s>>>(S.m, S.l0[0], S.l0[1], S.l0[2], S.G, S.slot_ids, S.slot_lvl,
+			                                                S.face_ell, S.face_fine, n_local, pslot, n, F, j0, t, ppos);
 		HIP_CHECK(hipGetLastError());
 	}
 }
@@ -302,7 +300,7 @@ void field_slope_pass(Grid& g, const uint64_t* refined_dev, size_t n_refined) {
 		return;
 	}
 	hipStream_t s = g.s_comp;
-	ensure_face(g);  // of the mesh about to be replaced
+	const FaceStencil S = face_stencil(g);  // of the mesh about to be replaced
 	DBuf<int32_t> pslot, err;
 	pslot.alloc(n_refined);
 	err.alloc(1);
@@ -312,8 +310,7 @@ void field_slope_pass(Grid& g, const uint64_t* refined_dev, size_t n_refined) {
 	g.fslopes.n = n_refined;
 	g.fslopes.t.alloc(3 * in.size() * n_refined);
 	g.fslopes.ppos.alloc(g.n_local);
-	k_field_slopes(g.m, g.l0, stretched_view(g), g.slot_ids.p, g.slot_lvl.p, g.face_ell.p, g.face_fine.p, g.n_local,
-	               pslot.p, n_refined, in.data(), int(in.size()), g.fslopes.t.p, g.fslopes.ppos.p, s);
+	k_field_slopes(S, g.n_local, pslot.p, n_refined, in.data(), int(in.size()), g.fslopes.t.p, g.fslopes.ppos.p, s);
 }
 
 void field_follow_restrict(Grid& g, const std::vector<int>& fids) {

@@ -32,7 +32,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "dccrgx_internal.hpp"
+#include "dccrgx_grid.hpp"
 
 namespace dccrgx {
 
@@ -104,13 +104,8 @@ __global__ void gol_amr_pack_kernel(const uint32_t* __restrict__ l0, const uint3
 // Entries without a slot hold kNoSlot and are skipped like same-parent ones.
 constexpr uint32_t kNoSlot = 0xffffffffu;
 
-// XCD-contiguous block order: hardware block b runs on XCD b % 8, so XCD x
-// gets the x-th eighth of the logical blocks and the rows neighboring its
-// rows (whose packed values it gathers) are fetched into its own L2 once,
-// not into all eight (gridDim.x is a multiple of 8)
-__device__ __forceinline__ uint32_t xcd_block() {
-	return (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-}
+// blocks in whole rounds over the 8 XCDs, for the kernels that take their
+// rows in xcd_block order (dccrgx_internal.hpp)
 __host__ __device__ constexpr unsigned xcd_grid(size_t blocks) { return unsigned((blocks + 7) / 8 * 8); }
 constexpr int kCollectRows = 256;
 constexpr uint32_t kCollectLds = 8192;  // packed entries staged per block (32 KB)
@@ -1216,6 +1211,135 @@ void k_gol_amr(int phase, GolAmrTables& T, size_t n_slots, size_t n_local, uint3
 			                                                                 s1, err);
 	}
 	HIP_CHECK(hipGetLastError());
+}
+
+// ---- the host side ------------------------------------------------------------
+namespace {
+// the fields of a phase or a turn, checked and marked written
+void gol_amr_fields(Grid& g, int sf, int lf, Field*& st, Field*& ls) {
+	st = &field(g, sf);
+	ls = &field(g, lf);
+	DX_REQUIRE(st->elem == 4, "game of life state must be a 4-byte field");
+	field_written(*st);
+	field_written(*ls);
+	DX_REQUIRE(ls->elem == 64, "live level-0 neighbor list must be a 64-byte field (8 x uint64)");
+}
+
+void gol_amr_ensure_tables(Grid& g) {
+	ensure_csr(g);
+	if (!g.gola.valid)
+		k_gol_amr_tables(g.m, g.slot_ids.p, g.n_slots, g.n_local, g.hood_len, g.nof_ptr.p, g.nof_slot.p, g.gola,
+		                 g.s_comp);
+}
+
+// The reference's two aborts from the error words of a turn, in the order the
+// reference would have aborted: h[0] the collect (the geometric one's or the
+// level-0 game's, replaced by h[1], the exact one's, when that had to run:
+// h[0] & exact_ran), then h[2] the spread.  (One phase: its word in h[0], the
+// rest zero.)
+void gol_amr_raise(const int h[3], int exact_ran) {
+	const int collect = (h[0] & exact_ran) ? h[1] : h[0];
+	for (int e : {collect, h[2]}) {
+		DX_REQUIRE(!(e & 1), "No more room in live neighbor list (more than 8 live level-0 neighbors)");
+		DX_REQUIRE(!(e & 2), "a dead neighbor's level-0 parent was recorded alive (siblings disagree)");
+	}
+}
+}  // namespace
+
+// get_live_neighbors of tests/game_of_life/solve.hpp:37-170, split at its
+// halo: phase 0 = the collect loop (46-110), phase 1 = spread + rule (113-167)
+void gol_amr_phase(Grid& g, int phase, int sf, int lf, int region) {
+	DX_REQUIRE(phase == 0 || phase == 1, "phase must be 0 (collect) or 1 (spread)");
+	Field *st, *ls;
+	gol_amr_fields(g, sf, lf, st, ls);
+	size_t s0, s1;
+	region_range(g, region, s0, s1);
+	if (s1 <= s0) return;
+	DBuf<int> err;
+	err.alloc(1);
+	gol_amr_ensure_tables(g);
+	HIP_CHECK(hipMemsetAsync(err.p, 0, sizeof(int), g.s_comp));
+	k_time_begin(g);
+	k_gol_amr(phase, g.gola, g.n_slots, g.n_local, (uint32_t*)st->data.p, (uint64_t*)ls->data.p, g.nof_ptr.p,
+	          g.nof_slot.p, s0, s1, err.p, g.s_comp);
+	k_time_end(g);
+	if (phase == 0) ls->local_zero = false;
+	int h[3] = {0, 0, 0};
+	d2h_small(h, err.p, sizeof(int), g.s_comp);
+	gol_amr_raise(h, 0);
+}
+
+// One turn of get_live_neighbors (tests/game_of_life/solve.hpp:37-170):
+// collect, the halo, spread + rule, and every local list error_cell-cleared
+// at the end as the reference's rule loop leaves it (163).  Collected lists
+// stay in the kernels' per-cell masks; only the cells other processes read
+// (the outer run) write theirs into list_field for the halo, then clear them.
+void gol_live_neighbors(Grid& g, int sf, int lf) {
+	Field *st, *ls;
+	gol_amr_fields(g, sf, lf, st, ls);
+	const size_t nl = g.n_local;
+	if (!nl && g.size == 1) return;
+	// err[0] the (geometric) collect, err[1] the exact collect, err[2]
+	// the spread: one host read per turn, at its end
+	DBuf<int> err;
+	err.alloc(3);
+	gol_amr_ensure_tables(g);
+	HIP_CHECK(hipMemsetAsync(err.p, 0, 3 * sizeof(int), g.s_comp));
+	uint64_t* L = reinterpret_cast<uint64_t*>(ls->data.p);
+	uint32_t* S = reinterpret_cast<uint32_t*>(st->data.p);
+	int h[3] = {0, 0, 0};
+	// the inner cells' lists are never written by the turn: clear them once
+	const bool lean = g.gola.mask_path;
+	if (lean && !ls->local_zero && g.n_inner) HIP_CHECK(hipMemsetAsync(L, 0, g.n_inner * 64, g.s_comp));
+	k_time_begin(g);
+	// one process: the level-0 game, the exact collect and spread only behind
+	// it (gated on the device) when a family disagrees
+	const bool level0_game = lean && g.gola.geo && g.gola.lg_layout && g.size == 1 && g.n_slots == nl &&
+	                         g.n_inner == nl && !std::getenv("DCCRGX_GOL_NO_L0GAME");
+	if (level0_game) {
+		k_gol_amr_level0_game(g.gola, g.d_hood.p, int(g.hood.size() / 3), S, nl, err.p, g.s_comp);
+		k_time_end(g);
+		d2h_small(h, err.p, sizeof(h), g.s_comp);
+		// every level-0 cell of a one-process grid has a known leaf
+		DX_REQUIRE(!(h[0] & 8), "internal error: the level-0 game met a level-0 cell without a known leaf");
+		if (h[0] & 4) {
+			// a family's leaves disagree (the game pass did not run): the
+			// exact collect and spread, whose abort order is the reference's
+			k_time_begin(g);
+			k_gol_amr(0, g.gola, g.n_slots, nl, S, L, g.nof_ptr.p, g.nof_slot.p, 0, nl, err.p + 1, g.s_comp,
+			          g.n_inner);
+			k_gol_amr(1, g.gola, g.n_slots, nl, S, L, g.nof_ptr.p, g.nof_slot.p, 0, nl, err.p + 2, g.s_comp, 0);
+			k_time_end(g);
+			d2h_small(h, err.p, sizeof(h), g.s_comp);
+		}
+		gol_amr_raise(h, 4);
+		ls->local_zero = true;
+		return;
+	}
+	if (lean && g.gola.geo) {
+		// the geometric collect; the exact per-entry one (gated on the
+		// device) when a family's leaves disagree or a reached level-0 cell
+		// is unknown - the reference's abort conditions then depend on the
+		// entry order
+		k_gol_amr_geo(g.gola, g.d_hood.p, int(g.hood.size() / 3), S, nl, nl + g.n_recv, L, g.n_inner, err.p,
+		              g.s_comp);
+		k_gol_amr(0, g.gola, g.n_slots, nl, S, L, g.nof_ptr.p, g.nof_slot.p, 0, nl, err.p + 1, g.s_comp, g.n_inner,
+		          err.p);
+	} else {
+		k_gol_amr(0, g.gola, g.n_slots, nl, S, L, g.nof_ptr.p, g.nof_slot.p, 0, nl, err.p, g.s_comp,
+		          lean ? g.n_inner : 0);
+	}
+	k_time_end(g);
+	halo_start(g);  // update_copies_of_remote_neighbors (solve.hpp:111)
+	halo_wait(g);
+	k_time_begin(g);
+	k_gol_amr(1, g.gola, g.n_slots, nl, S, L, g.nof_ptr.p, g.nof_slot.p, 0, nl, err.p + 2, g.s_comp);
+	k_time_end(g);
+	const size_t c0 = lean ? g.n_inner : 0;
+	if (nl > c0) HIP_CHECK(hipMemsetAsync(L + c0 * 8, 0, (nl - c0) * 64, g.s_comp));
+	d2h_small(h, err.p, sizeof(h), g.s_comp);
+	gol_amr_raise(h, 4 | 8);
+	ls->local_zero = true;
 }
 
 }  // namespace dccrgx

@@ -8,6 +8,12 @@
 #include <limits>
 #include <numeric>
 #include <set>
+#if DCCRGX_PHASE_TIMING
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+#endif
 
 #include "dccrgx_grid.hpp"
 
@@ -1269,6 +1275,50 @@ void migration_place_peer(Grid& g, int peer, const uint8_t* buf, size_t bytes) {
 	M.transferred = true;
 }
 
+// --------------------------------------------------------------------------- initialisation
+// shared by the setters of the C ABI, dccrgx_initialize and the grid-file loader
+
+// dccrg_mapping.hpp:316-329: the largest level whose ids fit in 64 bits
+int max_possible_level(const uint64_t len[3]) {
+	const double gl = double(len[0]) * double(len[1]) * double(len[2]);
+	int lvl = 0;
+	double cur = 0;
+	while (cur <= double(~uint64_t(0))) {
+		cur += gl * std::pow(8.0, double(lvl));
+		lvl++;
+	}
+	return lvl - 2;
+}
+
+// the largest neighborhood length whose neighbors_to dedupe fits in LDS
+unsigned max_hood_length() {
+	unsigned L = 0;
+	while (true) {
+		const unsigned n = (2 * (L + 1) + 1) * (2 * (L + 1) + 1) * (2 * (L + 1) + 1) - 1;
+		if (int(n) > max_hood_items()) return L;
+		L++;
+	}
+}
+
+void init_impl(Grid& g) {
+	DX_REQUIRE(!g.initialized, "already initialized");
+	map_init(g.m, g.len, g.R, g.per);
+	const unsigned L = g.hood_len;
+	const size_t cube = size_t(2 * L + 1) * (2 * L + 1) * (2 * L + 1);
+	std::vector<int32_t> h(3 * std::max<size_t>(cube, 6));
+	const int nh = default_hood(g.hood_len, h.data());
+	g.hood.assign(h.begin(), h.begin() + 3 * nh);
+	g.hood_to.resize(g.hood.size());
+	for (size_t i = 0; i < g.hood.size(); i++) g.hood_to[i] = -g.hood[i];
+	upload(g.d_hood, g.hood, g.s_comp);
+	upload(g.d_hood_to, g.hood_to, g.s_comp);
+	Mesh nm;
+	nm.implicit = true;
+	nm.bp.init(g.m.first[1] - 1, uint64_t(g.size));
+	rebuild(g, nm);
+	g.initialized = true;
+}
+
 // --------------------------------------------------------------------------- game of life, slab planes
 // The structured 26-point sweep needs the cells of a box in raster order.
 // On a uniform level-0 grid whose ranks hold whole z-planes (the block
@@ -1336,6 +1386,48 @@ bool gol_slab_plan(Grid& g, std::vector<GolBox>& inner, std::vector<GolBox>& out
 	return true;
 }
 
+// one step of the uniform game over a region into the field's scratch
+// (dccrgx_gol_step): the structured sweep over the slab plan's boxes, else the
+// CSR walk
+void gol_step(Grid& g, int sf, int region) {
+	Field& f = field(g, sf);
+	DX_REQUIRE(f.elem == 4, "game of life state must be a 4-byte field");
+	ensure_scratch(g, f);
+	size_t s0, s1;
+	region_range(g, region, s0, s1);
+	if (s1 <= s0) return;
+	if (!g.gol_plan_valid) {
+		g.gol_plan_ok = gol_slab_plan(g, g.gol_inner, g.gol_outer);
+		g.gol_plan_valid = true;
+	}
+	const uint32_t* st = (const uint32_t*)f.data.p;
+	uint32_t* out = (uint32_t*)f.scratch.p;
+	k_time_begin(g);
+	bool done = false;
+	if (g.gol_plan_ok) {
+		done = true;
+		for (int r = 0; r < 2 && done; r++) {
+			if (r == 0 && region == DCCRGX_REGION_OUTER) continue;
+			if (r == 1 && region == DCCRGX_REGION_INNER) continue;
+			for (const GolBox& b : r == 0 ? g.gol_inner : g.gol_outer) {
+				const uint64_t n[3] = {g.len[0], g.len[1], b.nz};
+				const int per[3] = {g.per[0], g.per[1], b.lo == -3 ? g.per[2] : 0};
+				const uint32_t* lo = b.lo >= 0 ? st + uint64_t(b.lo) : nullptr;
+				const uint32_t* hi = b.hi >= 0 ? st + uint64_t(b.hi) : nullptr;
+				if (!k_gol_structured(st + b.slot0, out + b.slot0, n, per, lo, hi, g.s_comp)) {
+					done = false;
+					break;
+				}
+			}
+		}
+	}
+	if (!done) {
+		ensure_csr(g);
+		k_gol_csr(st, out, g.it_ptr.p, g.it_slot.p, s0, s1, g.s_comp);
+	}
+	k_time_end(g);
+}
+
 // --------------------------------------------------------------------------- get_cells(criteria)
 // is_neighbor_type_match (dccrg.hpp:2946-3053) for every local row of a CSR pair
 __global__ void neighbor_types_kernel(DevMesh M, int rank, const uint32_t* of_ptr, const uint64_t* of_id,
@@ -1398,5 +1490,41 @@ std::vector<uint64_t> cells_by_criteria(Grid& g, const int32_t* crit, size_t nc,
 	std::sort(out.begin(), out.end());
 	return out;
 }
+
+#if DCCRGX_PHASE_TIMING
+namespace {
+struct PhaseTable {
+	std::map<std::string, std::pair<double, long>> t;
+	~PhaseTable() {
+		const char* r = std::getenv("RANK");
+		for (auto& kv : t)
+			std::fprintf(stderr, "[phase r%s] %-28s %10.3f ms total %7ld calls %9.3f ms/call\n", r ? r : "0",
+			             kv.first.c_str(), kv.second.first * 1e3, kv.second.second,
+			             kv.second.first * 1e3 / double(kv.second.second));
+	}
+};
+PhaseTable& phase_table() {
+	static PhaseTable pt;
+	return pt;
+}
+}  // namespace
+double PhaseScope::now() {
+	return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+void phase_add(const char* name, double seconds) {
+	auto& e = phase_table().t[name];
+	e.first += seconds;
+	e.second += 1;
+}
+void phase_reset() { phase_table().t.clear(); }
+double& phase_comm_total() {
+	static double t = 0;
+	return t;
+}
+long& phase_sync_count() {
+	static long k = 0;
+	return k;
+}
+#endif
 
 }  // namespace dccrgx

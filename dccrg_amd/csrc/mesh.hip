@@ -949,4 +949,44 @@ void known_leaves(Grid& g, std::vector<uint64_t>& ids, std::vector<int32_t>& own
 	}
 }
 
+namespace {
+// the device id math every build and sweep kernel uses (dccrgx_mapping.hpp),
+// evaluated for a batch of ids: 15 words per id (indices x3, length in
+// indices, parent, first child, level-0 parent, siblings x8)
+__global__ void mapping_batch_kernel(MapCtx m, const uint64_t* ids, size_t n, int32_t* level, uint64_t* out) {
+	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
+		uint64_t* o = out + 15 * i;
+		uint64_t x = 0, y = 0, z = 0;
+		const int l = map_indices(m, ids[i], x, y, z);
+		level[i] = l;
+		for (int k = 0; k < 15; k++) o[k] = error_cell;
+		if (l < 0) continue;
+		o[0] = x;
+		o[1] = y;
+		o[2] = z;
+		o[3] = map_cell_len(m, ids[i]);
+		o[4] = map_parent(m, ids[i]);
+		o[5] = map_child(m, ids[i]);
+		o[6] = map_level0_parent(m, ids[i]);
+		map_siblings(m, ids[i], o + 7);
+	}
+}
+}  // namespace
+
+void mapping_batch(Grid& g, const uint64_t* ids, size_t n, int32_t* level, uint64_t* out) {
+	if (!n) return;
+	MapCtx m;
+	map_init(m, g.len, g.R, g.per);
+	DBuf<uint64_t> d_ids, d_out;
+	DBuf<int32_t> d_lvl;
+	d_ids.alloc(n);
+	d_out.alloc(15 * n);
+	d_lvl.alloc(n);
+	h2d(d_ids.p, ids, n * 8, g.s_comp);
+	mapping_batch_kernel<<<grid_for(n, 256), 256, 0, g.s_comp>>>(m, d_ids.p, n, d_lvl.p, d_out.p);
+	HIP_CHECK(hipGetLastError());
+	HIP_CHECK(hipMemcpyAsync(level, d_lvl.p, n * 4, hipMemcpyDeviceToHost, g.s_comp));
+	d2h_small(out, d_out.p, 15 * n * 8, g.s_comp);
+}
+
 }  // namespace dccrgx

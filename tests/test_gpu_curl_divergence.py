@@ -1,5 +1,5 @@
 """dccrgx_curl, dccrgx_divergence and dccrgx_field_axpy (curl_kernel,
-divergence_kernel, field_axpy_kernel in dccrg_amd/csrc/poisson_kernels.hip).
+divergence_kernel, field_axpy_kernel in dccrg_amd/csrc/field_ops.hip).
 
 The main check is bitwise: the header defines both operators on top of
 dccrgx_gradient's derivative D_d(F), one IEEE operation per step, so a call

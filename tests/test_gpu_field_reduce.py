@@ -1,5 +1,5 @@
 """dccrgx_field_reduce / dccrgx_field_reduce_device (field_reduce_kernel and
-reduce_fold_kernel, dccrg_amd/csrc/poisson_kernels.hip) against
+reduce_fold_kernel, dccrg_amd/csrc/field_ops.hip) against
 tests/reduce_model.py.
 
 Both sides form bitwise equal terms (a * b, then * V for a sum by volume); only

@@ -135,6 +135,43 @@ def test_list_overflow_is_an_error(gpu):
     g.close()
 
 
+@pytest.mark.parametrize("no_l0game", [False, True])
+def test_list_overflow_through_the_whole_turn(gpu, monkeypatch, no_l0game):
+    """The same 9th live level-0 neighbor through get_live_neighbors, whose
+    error words are decoded at the turn's end: by default the level-0 game
+    runs (one process, nothing refined), with DCCRGX_GOL_NO_L0GAME=1 the
+    geometric collect; both raise the reference's message."""
+    if no_l0game:
+        monkeypatch.setenv("DCCRGX_GOL_NO_L0GAME", "1")
+    else:
+        monkeypatch.delenv("DCCRGX_GOL_NO_L0GAME", raising=False)
+    o = O.Grid((3, 3, 3), 1, (False, False, False), 1, 1)
+    g, st, ls = product_on(o, (3, 3, 3), (False, False, False))
+    st.set(np.ones(g.n_local, np.uint32))
+    with pytest.raises(dccrg_amd.DccrgError, match="No more room"):
+        g.get_live_neighbors(st, ls)
+    g.close()
+
+
+def test_disagreeing_family_without_the_level0_game(gpu, monkeypatch):
+    """The first case of test_turn_with_disagreeing_families_follows_the_reference
+    (child 0 alone alive) with the level-0 game switched off: the geometric
+    collect gives way to the exact one, and the turn's end raises the
+    reference's abort."""
+    monkeypatch.setenv("DCCRGX_GOL_NO_L0GAME", "1")
+    length = (6, 6, 1)
+    o = O.Grid(length, 1, (False, False, False), 1, 1)
+    o.refine_completely(15)
+    o.stop_refining()
+    g, st, ls = product_on(o, length, (False, False, False))
+    slots = g.slot_ids()[: g.n_local]
+    kids = np.sort(slots[slots > np.uint64(36)])
+    st.set((slots == kids[0]).astype(np.uint32))
+    with pytest.raises(dccrg_amd.DccrgError, match="recorded alive"):
+        g.get_live_neighbors(st, ls)
+    g.close()
+
+
 def test_siblings_disagreeing_is_an_error(gpu):
     """solve.hpp:81-90: a dead neighbor whose level-0 parent was already
     recorded alive through a sibling aborts the reference."""

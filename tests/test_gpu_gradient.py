@@ -1,4 +1,4 @@
-"""dccrgx_gradient (gradient_kernel, dccrg_amd/csrc/poisson_kernels.hip)
+"""dccrgx_gradient (gradient_kernel, dccrg_amd/csrc/field_ops.hip)
 against tests/gradient_model.py, which test_gradient_model_cpu.py pins.
 
 Both sides evaluate the header's contract one IEEE operation at a time, so a
