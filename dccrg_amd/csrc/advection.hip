@@ -11,7 +11,7 @@
 
 namespace dccrgx {
 
-// one of the advection switches DCCRGX_NBREC, LEN_TABLE, FACE_ONCE, REG3,
+// one of the advection switches DCCRGX_NBREC, LEN_TABLE, VEL_UNIFORM,
 // BAND_CACHE: whether the variable is set to `value` now (read per call:
 // tests switch them)
 static bool adv_switch(const char* name, int value = 1) {
@@ -80,13 +80,8 @@ const double* ensure_nbrec(Grid& g, const int fids[7]) {
 // then read without checking until a sweep finds the key unchanged.
 const double* ensure_len_table(Grid& g, const int fids[7], bool sweep) {
 	Grid::LenTable& L = g.lentab;
-	// the default kernels only: the experiment variants never take the table
-#if DCCRGX_FUSED_SWEEP
-	return nullptr;
-#endif
-	if (adv_switch("DCCRGX_LEN_TABLE", 0) || adv_switch("DCCRGX_NBREC") || adv_switch("DCCRGX_FACE_ONCE") ||
-	    adv_switch("DCCRGX_REG3"))
-		return nullptr;
+	// (the record kernels do not take the table)
+	if (adv_switch("DCCRGX_LEN_TABLE", 0) || adv_switch("DCCRGX_NBREC")) return nullptr;
 	if (!g.geo_block.empty() || g.n_slots == 0 || !g.tiles_valid) return nullptr;
 	if (!L.key.trackable(g, fids + 4)) return nullptr;
 	if (L.keyed && L.tiles_gen == g.tiles_gen && L.n_slots == g.n_slots && L.key.same(g, fids + 4) &&
@@ -165,6 +160,25 @@ VelMask ensure_vel_uniform(Grid& g, const int fids[7], bool sweep, const double*
 	return r;
 }
 
+// What a tile sweep of fields fids runs with, for every caller that sweeps
+// or reports on the sweep.  The three rules are written here and nowhere
+// else: the records exclude the table; a uniform component needs the table
+// and no records; the masks exist only in the register-length / level-row
+// builds of the length-table kernels (kRegMasks / kGenMasks).
+AdvSweepPlan adv_sweep_plan(Grid& g, const int fids[7], bool sweep) {
+	AdvSweepPlan P;
+	P.rec = ensure_nbrec(g, fids);
+	const double* len = ensure_len_table(g, fids, sweep);
+	// (the velocity key is followed whichever kernels run)
+	const VelMask vm = ensure_vel_uniform(g, fids, sweep, len);
+	P.len = P.rec ? nullptr : len;
+	const int um = P.len ? vm.mask : 0;
+	P.um[0] = kRegMasks ? um : 0;
+	P.um[1] = kGenMasks ? um : 0;
+	std::copy(vm.v, vm.v + 3, P.uv);
+	return P;
+}
+
 void advection_step(Grid& g, const int fids[7], double dt, int region) {
 	const double* f[7];
 	adv_fields(g, fids, f);
@@ -187,14 +201,12 @@ void advection_step(Grid& g, const int fids[7], double dt, int region) {
 	if (tiles) {
 		// (outside the timed interval: a rebuild happens once per mesh or
 		// field change, not per step)
-		const double* rec = ensure_nbrec(g, fids);
-		const double* len = ensure_len_table(g, fids, true);
-		const VelMask um = ensure_vel_uniform(g, fids, true, len);
+		const AdvSweepPlan plan = adv_sweep_plan(g, fids, true);
 		DX_LAP("step.0_nbrec");
 		k_time_begin(g);
 		// tiles never straddle the inner / outer runs
-		if (s0 < g.n_inner) k_advection_tiles(f, (double*)rho.scratch.p, g, 0, dt, g.s_comp, rec, len, um.mask, um.v);
-		if (s1 > g.n_inner) k_advection_tiles(f, (double*)rho.scratch.p, g, 1, dt, g.s_comp, rec, len, um.mask, um.v);
+		if (s0 < g.n_inner) k_advection_tiles(f, (double*)rho.scratch.p, g, 0, dt, g.s_comp, plan);
+		if (s1 > g.n_inner) k_advection_tiles(f, (double*)rho.scratch.p, g, 1, dt, g.s_comp, plan);
 	} else {
 		// the bands of the check that follows computed by the sweep (with the
 		// last check's parameters), recorded per run for band_cache_ok
@@ -260,8 +272,8 @@ void advection_layout(Grid& g, uint64_t out[12]) {
 	// density and one velocity (+ a level byte in the other tiles), an own
 	// cell 40 B (+ a level byte) instead of 64 B
 	uint64_t own = 64, lvl_byte = 0, uniform = 0;
-	const double* len = g.adv_fids_valid ? ensure_len_table(g, g.adv_fids, false) : nullptr;
-	if (len) {
+	const AdvSweepPlan plan = g.adv_fids_valid ? adv_sweep_plan(g, g.adv_fids, false) : AdvSweepPlan{};
+	if (plan.len) {
 		per_ext = 16;
 		lvl_byte = 1;
 		if (DCCRGX_LEN_OWN) own = 40;
@@ -270,7 +282,7 @@ void advection_layout(Grid& g, uint64_t out[12]) {
 		// across a side of its axis, and per general out-of-tile entry all of
 		// whose axis bits are uniform (it is then its density alone; an entry
 		// with another axis bit still counts the one velocity of per_ext)
-		const int um = DCCRGX_LEN_OWN && !DCCRGX_LEN_LDS ? ensure_vel_uniform(g, g.adv_fids, false, len).mask : 0;
+		const int um = plan.um[0];
 		if (um) {
 			Grid::VelUniform& U = g.veluni;
 			if (!U.ext_valid || U.ext_gen != g.tiles_gen) {
@@ -297,13 +309,9 @@ void advection_occupancy(Grid& g, uint64_t out[6]) {
 	ensure_tiles(g);
 	// the launch of the fields last passed to an advection call (before
 	// the first sweep: the one it will make)
-	const bool valid = g.adv_fids_valid;
-	const bool rec = valid && ensure_nbrec(g, g.adv_fids) != nullptr;
-	const double* tab = valid ? ensure_len_table(g, g.adv_fids, false) : nullptr;
-	const bool len = tab != nullptr;
-	const int um = valid ? ensure_vel_uniform(g, g.adv_fids, false, tab).mask : 0;
+	const AdvSweepPlan plan = g.adv_fids_valid ? adv_sweep_plan(g, g.adv_fids, false) : AdvSweepPlan{};
 	for (int kind = 0; kind < 2; kind++) {
-		const Grid::SweepLaunch& L = adv_sweep_launch(g, kind, rec, len, um);
+		const Grid::SweepLaunch& L = adv_sweep_launch(g, kind, plan);
 		int k = 0;
 		HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, L.fn, 512, L.lds));
 		out[3 * kind] = uint64_t(L.blocks_per_cu);
@@ -317,7 +325,7 @@ void advection_length_source(Grid& g, const int fids[7], int* out) {
 	const double* f[7];
 	adv_fields(g, fids, f);
 	ensure_tiles(g);
-	*out = ensure_len_table(g, fids, false) ? 1 : 0;
+	*out = adv_sweep_plan(g, fids, false).len ? 1 : 0;
 }
 
 void advection_velocity_source(Grid& g, const int fids[7], int* mask) {
@@ -325,7 +333,7 @@ void advection_velocity_source(Grid& g, const int fids[7], int* mask) {
 	const double* f[7];
 	adv_fields(g, fids, f);
 	ensure_tiles(g);
-	*mask = ensure_vel_uniform(g, fids, false, ensure_len_table(g, fids, false)).mask;
+	*mask = adv_sweep_plan(g, fids, false).um[0];
 }
 
 void advection_commit(Grid& g, int df) {

@@ -762,21 +762,6 @@ __global__ void carry_src_kernel(const uint64_t* __restrict__ slot_ids, size_t n
 	}
 }
 
-template <class T>
-__global__ void gather_rows_kernel(const T* __restrict__ old, const int32_t* __restrict__ src, size_t n,
-                                   T* __restrict__ out) {
-	for (size_t s = blockIdx.x * size_t(blockDim.x) + threadIdx.x; s < n; s += size_t(gridDim.x) * blockDim.x)
-		out[s] = src[s] >= 0 ? old[src[s]] : T{};
-}
-
-__global__ void gather_bytes_kernel(const uint8_t* __restrict__ old, const int32_t* __restrict__ src, size_t n,
-                                    size_t elem, uint8_t* __restrict__ out) {
-	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n * elem; i += size_t(gridDim.x) * blockDim.x) {
-		const size_t s = i / elem;
-		out[i] = src[s] >= 0 ? old[size_t(src[s]) * elem + (i - s * elem)] : uint8_t(0);
-	}
-}
-
 __global__ void morton_keys_kernel(MapCtx m, const uint64_t* ids, size_t n, uint64_t* keys) {
 	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
 		uint64_t x, y, z;
@@ -1844,19 +1829,6 @@ void k_carry_src(const uint64_t* slot_ids, size_t n_slots, size_t nl, const MapC
                  size_t old_n_local, int32_t* src, hipStream_t s) {
 	if (!n_slots) return;
 	carry_src_kernel<<<grid_for(n_slots, 256), 256, 0, s>>>(slot_ids, n_slots, nl, m, oldM, old_n_local, src);
-	HIP_CHECK(hipGetLastError());
-}
-
-void k_gather_rows(const uint8_t* old_data, const int32_t* src, size_t n, size_t elem, uint8_t* out, hipStream_t s) {
-	if (!n || !elem) return;
-	if (elem == 4)
-		gather_rows_kernel<uint32_t><<<grid_for(n, 256), 256, 0, s>>>((const uint32_t*)old_data, src, n, (uint32_t*)out);
-	else if (elem == 8)
-		gather_rows_kernel<uint64_t><<<grid_for(n, 256), 256, 0, s>>>((const uint64_t*)old_data, src, n, (uint64_t*)out);
-	else if (elem == 16)
-		gather_rows_kernel<uint4><<<grid_for(n, 256), 256, 0, s>>>((const uint4*)old_data, src, n, (uint4*)out);
-	else
-		gather_bytes_kernel<<<grid_for(n * elem, 256), 256, 0, s>>>(old_data, src, n, elem, out);
 	HIP_CHECK(hipGetLastError());
 }
 

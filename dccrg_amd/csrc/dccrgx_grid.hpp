@@ -46,15 +46,14 @@ void migration_place_peer(Grid& g, int peer, const uint8_t* buf, size_t bytes);
 
 std::vector<uint64_t> cells_by_criteria(Grid& g, const int32_t* crit, size_t nc, bool exact, int hood);
 int64_t host_slot_of(Grid& g, uint64_t id);
-bool gol_slab_plan(Grid& g, std::vector<GolBox>& inner, std::vector<GolBox>& outer);
 // grid.hip: what the setters, dccrgx_initialize and the grid-file loader
 // share: the limits of the refinement level and of the neighborhood length,
 // and the first build of the mesh
 int max_possible_level(const uint64_t len[3]);
 unsigned max_hood_length();
 void init_impl(Grid& g);
-// grid.hip: dccrgx_gol_step, one step of the uniform game of life into the
-// state field's scratch
+// gol.hip: dccrgx_gol_step, one step of the uniform game of life into the
+// state field's scratch (kernels and driver)
 void gol_step(Grid& g, int sf, int region);
 // gol_amr.hip: the refined game of life, one phase (0 collect, 1 spread) over
 // a region or a whole turn with its halo; the reference's aborts are raised

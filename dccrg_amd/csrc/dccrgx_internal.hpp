@@ -843,13 +843,8 @@ struct Grid {
 	// the pipelined kernel's capacities (> 1024 ext cells or > 512 finer
 	// faces): the run is then swept by the untiled face-CSR kernel
 	DBuf<uint32_t> tmeta;
-	// both kinds in tile order per run (advection_fused_kernel), 8 x u32 per
-	// tile, word 7 = 1 for a regular tile (then RegTileMeta's words), 0 for
-	// another (then tmeta's); empty with tmeta
-	DBuf<uint32_t> tfused;
-	size_t tfused_n[2] = {0, 0};
 	uint64_t tiles_gen = 0;  // bumped by every tile build
-	// Neighbor records of the tile sweeps (sweep_kernels.hip, built by
+	// Neighbor records of the tile sweeps (advection_sweep.hip, built by
 	// ensure_nbrec): per axis a and slot s one 24-B record {l_a, l_b * l_c,
 	// v_a} (b < c the other two axes, the product as the reference forms the
 	// face area) at r[(3 a n_slots + 3 s) ..], so an out-of-tile face neighbor
@@ -914,7 +909,7 @@ struct Grid {
 	// launched with, and the blocks per CU the runtime reports for that launch
 	// (adv_sweep_launch; cached on the kernel and the LDS size)
 	struct SweepLaunch {
-		const void* fn = nullptr;
+		void* fn = nullptr;
 		size_t lds_min = 0, lds = 0;
 		int blocks_per_cu = 0;
 	} adv_launch[2];
@@ -1121,7 +1116,6 @@ void k_face_csr(const int32_t* ell, const int32_t* fine, size_t nrows, DBuf<uint
                 hipStream_t s);
 void k_carry_src(const uint64_t* slot_ids, size_t n_slots, size_t nl, const MapCtx& m, const DevMesh& oldM,
                  size_t old_n_local, int32_t* src, hipStream_t s);
-void k_gather_rows(const uint8_t* old_data, const int32_t* src, size_t n, size_t elem, uint8_t* out, hipStream_t s);
 // ghost region: the level-0 cells within `radius` of the level-0 parent of a
 // local cell that are not wholly owned here (sorted, unique)
 std::vector<uint64_t> k_ghost_level0(const MapCtx& m, const DevMesh& M, int rank, const uint64_t* local, size_t n,
@@ -1183,42 +1177,34 @@ TileBuild k_build_tiles(const uint32_t* face_ptr, const int32_t* face_ent, const
 void k_classify_tiles(const MapCtx& m, const uint32_t* tstart, size_t n_tiles_inner, size_t n_tiles_outer,
                       const uint64_t* slot_ids, const int32_t* face_ell, DBuf<uint32_t>& lists, DBuf<int32_t>& tnb,
                       DBuf<RegTileMeta>& regmeta, size_t counts[4], hipStream_t s);
+// the level bytes the length-table sweeps read: of every ext_pk entry's slot
+// into ext_lvl, of every regular tile into its record's last word
+void k_tile_levels(const uint8_t* slot_lvl, const uint32_t* ext_pk, size_t n_ext, uint8_t* ext_lvl,
+                   RegTileMeta* regmeta, size_t n_reg, hipStream_t s);
 
-// --- launchers implemented in sweep_kernels.hip -----------------------------
+// --- launchers implemented in payload.hip -----------------------------------
 // gather bytes [off, off + len) of the elements at `slots` into `out`
 void k_pack(const uint8_t* field, size_t elem, size_t off, size_t len, const int32_t* slots, size_t n, uint8_t* out,
             hipStream_t s);
 // scatter: inverse of k_pack
 void k_place(const uint8_t* in, size_t elem, size_t off, size_t len, const int32_t* slots, size_t n, uint8_t* field,
              hipStream_t s);
-void k_gol_csr(const uint32_t* state, uint32_t* out, const uint32_t* it_ptr, const int32_t* it_slot, size_t s0,
-               size_t s1, hipStream_t s);
-// uniform 26-point game of life on a box of nx x ny x nz cells stored in
-// raster order; planes z = -1 and z = nz come from lo / hi (nullptr: outside)
-bool k_gol_structured(const uint32_t* state, uint32_t* out, const uint64_t n[3], const int per[3], const uint32_t* lo,
-                      const uint32_t* hi, hipStream_t s);
-void k_advection(const double* const f[7], double* rho_out, const uint32_t* face_ptr, const int32_t* face_ent,
-                 size_t s0, size_t s1, double dt, hipStream_t s);
-// tiled advection sweep over the regular and the irregular tiles of one run
-// (run 0 inner, 1 outer: tiles never straddle the two)
-void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int run, double dt, hipStream_t s,
-                       const double* nbrec = nullptr, const double* lentab = nullptr, int um = 0,
-                       const double uniform[3] = nullptr);
+// out row s = old row src[s] (elem bytes each), zeros where src[s] < 0
+void k_gather_rows(const uint8_t* old_data, const int32_t* src, size_t n, size_t elem, uint8_t* out, hipStream_t s);
+
+// --- launchers implemented in advection_sweep.hip; the caches and the plan --
+// --- of the sweep they serve (ensure_*, adv_sweep_plan) are advection.hip's -
 // the per-level length table (32 rows of lx, ly, lz) for the sweep of fields
 // fids when every slot's three lengths are bitwise their level's row, checked
 // by one device pass and cached (Grid::LenTable); nullptr - the sweeps read
 // the length fields - otherwise, when a length field is external, a stretched
-// geometry is held, DCCRGX_LEN_TABLE=0, or an experiment variant of the tile
-// kernels is selected (advection.hip).  sweep: the call precedes a sweep (a key found changed
-// at two sweeps in a row backs off to the fields without checking)
+// geometry is held, DCCRGX_LEN_TABLE=0 or DCCRGX_NBREC=1 (advection.hip).
+// sweep: the call precedes a sweep (a key found changed at two sweeps in a
+// row backs off to the fields without checking)
 const double* ensure_len_table(Grid& g, const int fids[7], bool sweep);
 // 1 when a slot's lengths differ from its level's row of tab (else 0) into flag
 void k_len_check(const double* const f[7], const uint8_t* slot_lvl, size_t n, const double* tab, int* flag,
                  hipStream_t s);
-// the level bytes the length-table sweeps read: of every ext_pk entry's slot
-// into ext_lvl, of every regular tile into its record's last word
-void k_tile_levels(const uint8_t* slot_lvl, const uint32_t* ext_pk, size_t n_ext, uint8_t* ext_lvl,
-                   RegTileMeta* regmeta, size_t n_reg, hipStream_t s);
 // own cells' lengths from the table too (0: only the out-of-tile neighbors',
 // the first stage of the change, kept for paired A/Bs)
 #ifndef DCCRGX_LEN_OWN
@@ -1243,11 +1229,6 @@ void k_tile_levels(const uint8_t* slot_lvl, const uint32_t* ext_pk, size_t n_ext
 #ifndef DCCRGX_GEN_BLOCKS
 #define DCCRGX_GEN_BLOCKS ((DCCRGX_LEN_OWN && !DCCRGX_LEN_LDS_GEN) ? 3 : 2)
 #endif
-// the launch k_advection_tiles makes (or would make, given whether the
-// neighbor records / the length table are in use) for the regular (kind 0)
-// or the other tiles (kind 1): fills and returns g.adv_launch[kind]
-// um: the mask of uniform velocity components (length-table kernels only)
-const Grid::SweepLaunch& adv_sweep_launch(Grid& g, int kind, bool nbrec, bool lentab, int um = 0);
 // The uniform velocity components of the sweep of fields fids: bit a of mask
 // set - every slot of component a (remote copies too) holds the 64-bit
 // pattern of v[a], checked by one device pass and cached (Grid::VelUniform).
@@ -1273,6 +1254,30 @@ void k_ext_axis_count(const uint32_t* tmeta, size_t ntiles, const uint32_t* ext_
 // (or DCCRGX_NBREC=0): the sweeps then read the fields (advection.hip)
 const double* ensure_nbrec(Grid& g, const int fids[7]);
 void k_nbrec(const double* const f[7], size_t n, double* r, hipStream_t s);
+// the uniform-velocity masks exist in the register-length (regular tiles) /
+// level-row (other tiles) builds of the length-table kernels only
+constexpr bool kRegMasks = DCCRGX_LEN_OWN && !DCCRGX_LEN_LDS, kGenMasks = DCCRGX_LEN_OWN && !DCCRGX_LEN_LDS_GEN;
+// What a tile sweep of fields fids runs with (adv_sweep_plan, advection.hip:
+// the one place that decides it): the neighbor records or the per-level
+// length table (never both, nullptr: the kernels read the fields), and per
+// kind of tile (0 regular, 1 other) the mask of uniform velocity components,
+// whose values are uv.  The kernels and their launch follow from it alone.
+struct AdvSweepPlan {
+	const double* rec = nullptr;
+	const double* len = nullptr;
+	int um[2] = {0, 0};
+	double uv[3] = {0, 0, 0};
+};
+// sweep: the call precedes a sweep (ensure_len_table, ensure_vel_uniform)
+AdvSweepPlan adv_sweep_plan(Grid& g, const int fids[7], bool sweep);
+// tiled advection sweep over the regular and the irregular tiles of one run
+// (run 0 inner, 1 outer: tiles never straddle the two)
+void k_advection_tiles(const double* const f[7], double* rho_out, Grid& g, int run, double dt, hipStream_t s,
+                       const AdvSweepPlan& plan);
+// the launch k_advection_tiles makes (or would make) with `plan` for the
+// regular (kind 0) or the other tiles (kind 1): fills and returns
+// g.adv_launch[kind]
+const Grid::SweepLaunch& adv_sweep_launch(Grid& g, int kind, const AdvSweepPlan& plan);
 // the bands of check_for_adaptation (adv_bands_kernel) written by the sweep
 // as well, for rows [s0, s1) of `band`
 struct BandArgs {
@@ -1284,13 +1289,15 @@ struct BandArgs {
 };
 void k_advection_ell(const double* const f[7], double* rho_out, const int32_t* ell, const int32_t* fine, size_t s0,
                      size_t s1, double dt, hipStream_t s, const BandArgs* bands = nullptr);
+
+// --- launchers implemented in advection_adapt.hip ---------------------------
 void k_adv_dt(const double* const f[7], size_t n, double* partial, size_t nblocks, hipStream_t s);
 void k_min_partials(const double* partial, size_t n, double* out, hipStream_t s);
 size_t k_adv_candidates(const MapCtx& m, const double* rho, const FaceView& F, const uint8_t* lvl8, size_t n,
                         double diff_increase, double diff_threshold, uint64_t* out, hipStream_t s);
 // adaptation of tests/advection/adapter.hpp: per local cell band (2 refine,
 // 1 keep, 0 unrefine), merged parents' densities, velocity + length reset
-// check_for_adaptation's requests computed on the device (sweep_kernels.hip
+// check_for_adaptation's requests computed on the device (advection_adapt.hip
 // adv_requests_kernel): refine ids, unrefine ids of whole local families,
 // the number of kept whole families, and the partial runs (first slot,
 // length, members' ids and bands) for the host to merge by parent
@@ -1314,6 +1321,13 @@ void k_adv_bands(const MapCtx& m, const double* rho, const FaceView& F, const ui
 // process: exactly the removed cells' parents; used when 8 np removed cells)
 void k_adv_merge_parents(const MapCtx& m, const DevMesh& dm, size_t n_local, LazyIds& rm, double* rho,
                          const double* removed_rho, hipStream_t s, const uint64_t* parents = nullptr, size_t np = 0);
+// (dt_partial: when given, the block minima of the time-step bound of the
+// values written, as k_adv_dt computes them; returns their count)
+constexpr unsigned kDtPartials = 2048;  // block minima a reset pass leaves at most
+// (G.c given: centers and lengths of the stretched geometry instead of start / l0's)
+size_t k_adv_reset(const MapCtx& m, const uint64_t* slot_ids, size_t n, const double start[3], const double l0[3],
+                   const StretchedView& G, double* const f[7], hipStream_t s, double* dt_partial = nullptr);
+
 // ---- cell fields follow the mesh (field_adapt.hip) --------------------------
 // up to kFollowBatch fp64 fields of one restriction launch: the new array,
 // the removed store and the mode (DCCRGX_FOLLOW_*) of each
@@ -1343,12 +1357,6 @@ void k_field_slopes(const FaceStencil& F, size_t n_local, const int32_t* pslot, 
 void k_field_follow_gather(const MapCtx& m, const double* old_data, const int32_t* src, size_t n_slots, size_t n_local,
                            const uint64_t* slot_ids, const uint64_t* old_slot_ids, int mode, const double* t,
                            const int32_t* ppos, size_t n_ppos, size_t n_refined, double* out, hipStream_t s);
-// (dt_partial: when given, the block minima of the time-step bound of the
-// values written, as k_adv_dt computes them; returns their count)
-constexpr unsigned kDtPartials = 2048;  // block minima a reset pass leaves at most
-// (G.c given: centers and lengths of the stretched geometry instead of start / l0's)
-size_t k_adv_reset(const MapCtx& m, const uint64_t* slot_ids, size_t n, const double start[3], const double l0[3],
-                   const StretchedView& G, double* const f[7], hipStream_t s, double* dt_partial = nullptr);
 void k_time_begin(Grid& g);
 void k_time_end(Grid& g);
 

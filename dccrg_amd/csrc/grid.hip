@@ -1319,115 +1319,6 @@ void init_impl(Grid& g) {
 	g.initialized = true;
 }
 
-// --------------------------------------------------------------------------- game of life, slab planes
-// The structured 26-point sweep needs the cells of a box in raster order.
-// On a uniform level-0 grid whose ranks hold whole z-planes (the block
-// partition, or any repartition into z-planes) a rank holds its planes in
-// slot order [inner planes | outer planes] and receives each neighbor plane as
-// one contiguous run of halo slots, so every region is a set of boxes whose
-// z-1 / z+1 planes are other runs.
-static int64_t plane_slot(Grid& g, int64_t z) {
-	const int64_t nz = int64_t(g.len[2]);
-	if (z < 0 || z >= nz) {
-		if (!g.per[2]) return -2;  // outside the grid
-		z = (z % nz + nz) % nz;
-	}
-	const uint64_t plane = g.len[0] * g.len[1];
-	const uint64_t first = 1 + uint64_t(z) * plane, last = first + plane - 1;
-	const int64_t a = lookup_slot(g, first), b = lookup_slot(g, last);
-	if (a < 0 || b != a + int64_t(plane) - 1) return -1;  // not one contiguous run
-	return a;
-}
-
-bool gol_slab_plan(Grid& g, std::vector<GolBox>& inner, std::vector<GolBox>& outer) {
-	inner.clear();
-	outer.clear();
-	if (g.R != 0 || g.hood_len != 1 || g.len[0] % 256 != 0) return false;
-	const uint64_t plane = g.len[0] * g.len[1];
-	const int64_t nz = int64_t(g.len[2]);
-	if (!g.n_local || g.n_local % plane != 0) return false;
-	if (g.size == 1 && g.n_outer == 0 && g.n_slots == g.n_local && g.n_local == plane * uint64_t(nz)) {
-		inner.push_back(GolBox{0, uint64_t(nz), -3, -3});  // -3: the kernel's own periodic wrap
-		return true;
-	}
-	// the own cells must be whole planes, each one run of local slots of one
-	// class (inner or outer); any number of z runs (e.g. a rank holding two
-	// slabs after a repartition)
-	std::vector<int64_t> own(size_t(nz), -1);
-	uint64_t owned = 0;
-	for (int64_t z = 0; z < nz; z++) {
-		const int64_t s0 = plane_slot(g, z);
-		if (s0 < 0 || uint64_t(s0) + plane > g.n_local) continue;
-		if ((uint64_t(s0) < g.n_inner) != (uint64_t(s0) + plane - 1 < g.n_inner)) return false;
-		own[size_t(z)] = s0;
-		owned++;
-	}
-	if (owned * plane != g.n_local) return false;
-	auto slot = [&](int64_t z) -> int64_t {
-		return (z >= 0 && z < nz && own[size_t(z)] >= 0) ? own[size_t(z)] : plane_slot(g, z);
-	};
-	// boxes: runs of inner planes consecutive in z and in slots; every outer
-	// plane alone; z-1 / z+1 of a box: another run (local or halo) or nothing
-	for (int64_t z = 0; z < nz;) {
-		if (own[size_t(z)] < 0) {
-			z++;
-			continue;
-		}
-		const bool in = uint64_t(own[size_t(z)]) < g.n_inner;
-		int64_t e = z + 1;
-		while (in && e < nz && own[size_t(e)] >= 0 && uint64_t(own[size_t(e)]) < g.n_inner &&
-		       own[size_t(e)] == own[size_t(e - 1)] + int64_t(plane))
-			e++;
-		const int64_t lo = slot(z - 1), hi = slot(e);
-		if (lo == -1 || hi == -1) return false;  // a neighbor plane not held as one run
-		(in ? inner : outer).push_back(GolBox{uint64_t(own[size_t(z)]), uint64_t(e - z), lo, hi});
-		z = e;
-	}
-	return true;
-}
-
-// one step of the uniform game over a region into the field's scratch
-// (dccrgx_gol_step): the structured sweep over the slab plan's boxes, else the
-// CSR walk
-void gol_step(Grid& g, int sf, int region) {
-	Field& f = field(g, sf);
-	DX_REQUIRE(f.elem == 4, "game of life state must be a 4-byte field");
-	ensure_scratch(g, f);
-	size_t s0, s1;
-	region_range(g, region, s0, s1);
-	if (s1 <= s0) return;
-	if (!g.gol_plan_valid) {
-		g.gol_plan_ok = gol_slab_plan(g, g.gol_inner, g.gol_outer);
-		g.gol_plan_valid = true;
-	}
-	const uint32_t* st = (const uint32_t*)f.data.p;
-	uint32_t* out = (uint32_t*)f.scratch.p;
-	k_time_begin(g);
-	bool done = false;
-	if (g.gol_plan_ok) {
-		done = true;
-		for (int r = 0; r < 2 && done; r++) {
-			if (r == 0 && region == DCCRGX_REGION_OUTER) continue;
-			if (r == 1 && region == DCCRGX_REGION_INNER) continue;
-			for (const GolBox& b : r == 0 ? g.gol_inner : g.gol_outer) {
-				const uint64_t n[3] = {g.len[0], g.len[1], b.nz};
-				const int per[3] = {g.per[0], g.per[1], b.lo == -3 ? g.per[2] : 0};
-				const uint32_t* lo = b.lo >= 0 ? st + uint64_t(b.lo) : nullptr;
-				const uint32_t* hi = b.hi >= 0 ? st + uint64_t(b.hi) : nullptr;
-				if (!k_gol_structured(st + b.slot0, out + b.slot0, n, per, lo, hi, g.s_comp)) {
-					done = false;
-					break;
-				}
-			}
-		}
-	}
-	if (!done) {
-		ensure_csr(g);
-		k_gol_csr(st, out, g.it_ptr.p, g.it_slot.p, s0, s1, g.s_comp);
-	}
-	k_time_end(g);
-}
-
 // --------------------------------------------------------------------------- get_cells(criteria)
 // is_neighbor_type_match (dccrg.hpp:2946-3053) for every local row of a CSR pair
 __global__ void neighbor_types_kernel(DevMesh M, int rank, const uint32_t* of_ptr, const uint64_t* of_id,

@@ -925,7 +925,7 @@ void k_classify_tiles(const MapCtx& m, const uint32_t* tstart, size_t n_tiles_in
 	HIP_CHECK(hipStreamSynchronize(s));
 }
 
-// The level bytes of the length-table sweeps (sweep_kernels.hip): entry k of
+// The level bytes of the length-table sweeps (advection_sweep.hip): entry k of
 // ext_lvl is the level of ext_pk[k]'s slot, read coalesced with the ext code
 // (no gather into slot_lvl during the sweep); a regular tile is one level by
 // construction, its first slot's goes into the record's last word.

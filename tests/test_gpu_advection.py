@@ -117,7 +117,7 @@ def test_inner_outer_split_equals_all(gpu):
 @pytest.mark.parametrize("base,R", [((32, 32, 8), 2), ((12, 12, 3), 2), ((10, 10, 4), 1)])
 def test_face_table_sweep_bitwise_equals_tiles(gpu, base, R):
     """The first step on a freshly built mesh sweeps the fixed-width face
-    table (advection_ell_kernel) instead of building tiles; the tiles come
+    table (advection_ell_lds_kernel) instead of building tiles; the tiles come
     with the second step.  A grid whose tiles are built up front
     (advection_layout) gives bitwise the same densities at every step."""
     out = []
@@ -335,7 +335,7 @@ def nbrec_on(monkeypatch):
 @pytest.mark.parametrize("base,R", [((32, 32, 8), 2), ((12, 12, 3), 2), ((10, 10, 4), 1)])
 def test_neighbor_records_bitwise_equal_fields(gpu, nbrec_on, base, R):
     """The tile sweeps read an out-of-tile neighbor's length, face area and
-    velocity from its per-axis record (NbRecords, sweep_kernels.hip) instead
+    velocity from its per-axis record (NbRecords, advection_sweep.hip) instead
     of the fields; staged as (l_a, area, 1.0) every flux forms the same
     products, so the densities are bitwise those of the field reads (here
     forced by handing out a velocity field's device pointer)."""

@@ -24,9 +24,8 @@ Kernel paths (PATHS), each on every mesh of MESHES where it can be reached:
            kernels also see the first step's state
   vz0      vz exactly 0 in a tenth of the cells (the isnormal rule of the
            time step; a zero face velocity), on three meshes
-The switches read once per process (DCCRGX_REG3, DCCRGX_FACE_ONCE,
-DCCRGX_ELL_LDS, DCCRGX_TILES) and the compile-time fused sweep cannot be
-flipped by a test and are not covered.
+DCCRGX_TILES is the only switch read once per process: a test cannot flip
+it, so its two overrides are not covered.
 
 Meshes, with what advection_layout() must report so that a mesh cannot
 silently stop exercising its kernel: see LAYOUT."""
