@@ -179,6 +179,7 @@ _SIGS = {
     "dccrgx_advection_occupancy": (C.c_int, [vp, P(u64)]),
     "dccrgx_advection_length_source": (C.c_int, [vp, P(C.c_int), P(C.c_int)]),
     "dccrgx_advection_velocity_source": (C.c_int, [vp, P(C.c_int), P(C.c_int)]),
+    "dccrgx_advection_divide_source": (C.c_int, [vp, P(C.c_int), P(C.c_int)]),
     "dccrgx_poisson_cache": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, sz]),
     "dccrgx_poisson_solve": (C.c_int, [vp, C.c_uint, C.c_uint, C.c_double, C.c_double, C.c_double, C.c_int,
                                        P(C.c_uint), P(C.c_double)]),

@@ -12,8 +12,8 @@
 namespace dccrgx {
 
 // one of the advection switches DCCRGX_NBREC, LEN_TABLE, VEL_UNIFORM,
-// BAND_CACHE: whether the variable is set to `value` now (read per call:
-// tests switch them)
+// DIV_POW2, BAND_CACHE: whether the variable is set to `value` now (read per
+// call: tests switch them)
 static bool adv_switch(const char* name, int value = 1) {
 	const char* e = std::getenv(name);
 	return e && std::atoi(e) == value;
@@ -67,6 +67,40 @@ const double* ensure_nbrec(Grid& g, const int fids[7]) {
 	return R.r.p;
 }
 
+// a finite, positive, normal double with a zero mantissa
+static bool normal_pow2(double x) {
+	uint64_t b;
+	std::memcpy(&b, &x, sizeof(b));
+	const uint64_t e = (b >> 52) & 0x7ffu;
+	return (b >> 63) == 0 && e != 0 && e != 0x7ffu && (b & ((uint64_t(1) << 52) - 1)) == 0;
+}
+
+// The reciprocals behind the 96 lengths of table h (kLenTabP2 doubles): per
+// level 1 / (2 l_a), the divisor of a face between two cells of that level,
+// and 1 / (lx ly lz), the product in the kernels' operand order.  True when
+// the sweeps may multiply by them instead of dividing: each l0 and, at every
+// level, each length, divisor and reciprocal is a normal power of two, so
+// the reciprocal is exact and the product rounds the real number the
+// quotient rounds.  One verdict for the three axes; the entries are written
+// either way (a false verdict leaves them unread).
+static bool len_table_reciprocals(const double l0[3], double* h) {
+	bool ok = normal_pow2(l0[0]) && normal_pow2(l0[1]) && normal_pow2(l0[2]);
+	auto reciprocal = [&](double d) {
+		const double r = 1.0 / d;
+		ok = ok && normal_pow2(d) && normal_pow2(r) && r * d == 1.0;
+		return r;
+	};
+	for (int lvl = 0; lvl < 32; lvl++) {
+		const double* row = h + 3 * lvl;
+		for (int d = 0; d < 3; d++) {
+			ok = ok && normal_pow2(row[d]);
+			h[96 + 3 * lvl + d] = reciprocal(row[d] + row[d]);
+		}
+		h[192 + lvl] = reciprocal(row[0] * row[1] * row[2]);
+	}
+	return ok;
+}
+
 // The per-level length table of the tile sweeps (Grid::LenTable) for the
 // fields fids, or nullptr: the sweeps read the length fields.  The table is
 // l0[d] * (1 / 2^level), the expression of dccrgx_advection_initialize and of
@@ -98,10 +132,11 @@ const double* ensure_len_table(Grid& g, const int fids[7], bool sweep) {
 		if (sweep && ++L.changed >= 2) return nullptr;
 	}
 	if (!L.tab.p || L.tab_l0[0] != g.l0[0] || L.tab_l0[1] != g.l0[1] || L.tab_l0[2] != g.l0[2]) {
-		double h[96];
+		double h[kLenTabP2];
 		for (int lvl = 0; lvl < 32; lvl++)
 			for (int d = 0; d < 3; d++) h[3 * lvl + d] = g.l0[d] * (1.0 / double(uint64_t(1) << lvl));
-		L.tab.alloc(96);
+		L.pow2 = len_table_reciprocals(g.l0, h);
+		L.tab.alloc(kLenTabP2);
 		L.flag.alloc(1);
 		h2d(L.tab.p, h, sizeof(h), g.s_comp);
 		HIP_CHECK(hipStreamSynchronize(g.s_comp));  // h is a local
@@ -161,10 +196,13 @@ VelMask ensure_vel_uniform(Grid& g, const int fids[7], bool sweep, const double*
 }
 
 // What a tile sweep of fields fids runs with, for every caller that sweeps
-// or reports on the sweep.  The three rules are written here and nowhere
+// or reports on the sweep.  The four rules are written here and nowhere
 // else: the records exclude the table; a uniform component needs the table
 // and no records; the masks exist only in the register-length / level-row
-// builds of the length-table kernels (kRegMasks / kGenMasks).
+// builds of the length-table kernels (kRegMasks / kGenMasks); the kernels
+// multiply by the table's reciprocals (pow2) with the table, where the host
+// found every divisor a power of two (LenTable::pow2), in those builds, and
+// unless DCCRGX_DIV_POW2=0.
 AdvSweepPlan adv_sweep_plan(Grid& g, const int fids[7], bool sweep) {
 	AdvSweepPlan P;
 	P.rec = ensure_nbrec(g, fids);
@@ -176,6 +214,7 @@ AdvSweepPlan adv_sweep_plan(Grid& g, const int fids[7], bool sweep) {
 	P.um[0] = kRegMasks ? um : 0;
 	P.um[1] = kGenMasks ? um : 0;
 	std::copy(vm.v, vm.v + 3, P.uv);
+	P.pow2 = P.len && g.lentab.pow2 && kRegMasks && kGenMasks && !adv_switch("DCCRGX_DIV_POW2", 0);
 	return P;
 }
 
@@ -334,6 +373,14 @@ void advection_velocity_source(Grid& g, const int fids[7], int* mask) {
 	adv_fields(g, fids, f);
 	ensure_tiles(g);
 	*mask = adv_sweep_plan(g, fids, false).um[0];
+}
+
+void advection_divide_source(Grid& g, const int fids[7], int* out) {
+	DX_REQUIRE(out, "null output");
+	const double* f[7];
+	adv_fields(g, fids, f);
+	ensure_tiles(g);
+	*out = adv_sweep_plan(g, fids, false).pow2 ? 1 : 0;
 }
 
 void advection_commit(Grid& g, int df) {

@@ -32,6 +32,19 @@ __device__ __forceinline__ double adv_face_flux(int dir, double cd, double cl_a,
 	return (v >= 0 ? nd : cd) * dt * v * min_area;
 }
 
+// The same flux through a face between two cells of one level, whose lengths
+// are then the same bits (the length table's row): cl_a + nl_a = 2 cl_a is a
+// power of two and rinv its reciprocal (Grid::LenTable::pow2), so the product
+// is bitwise the quotient, and fmin of the two equal areas is the area.
+__device__ __forceinline__ double adv_face_flux_same(int dir, double cd, double cl_a, double cl_b, double cl_c,
+                                                     double cvel, double nd, double nv, double rinv, double dt) {
+#pragma clang fp contract(off)
+	const double min_area = cl_b * cl_c;
+	const double v = (cl_a * nv + cl_a * cvel) * rinv;
+	if (dir & 1) return -((v >= 0 ? cd : nd) * dt * v * min_area);
+	return (v >= 0 ? nd : cd) * dt * v * min_area;
+}
+
 struct AdvNb {
 	double d, lx, ly, lz, v;
 };
@@ -231,15 +244,20 @@ struct AdvPtrs {
 // -G, the plus-side cell +G; evaluated from the plus side the reference
 // computes the same products in swapped (commutative) order, so one
 // evaluation per face is bitwise what each side would get.
+// P2: ca + na is a power of two and rinv its reciprocal, a normal double
+// (Grid::LenTable::pow2): the product rounds the real number the quotient
+// rounds, so v has the same bits for every numerator.
+template <bool P2 = false>
 __device__ __forceinline__ double adv_face_g(int a, double cd, double clx, double cly, double clz, double cv_a,
-                                             const AdvNb& n, double dt) {
+                                             const AdvNb& n, double dt, double rinv = 0) {
 #pragma clang fp contract(off)
 	double ca, cb, cc, na, nb, nc;
 	if (a == 0) { ca = clx; cb = cly; cc = clz; na = n.lx; nb = n.ly; nc = n.lz; }
 	else if (a == 1) { ca = cly; cb = clx; cc = clz; na = n.ly; nb = n.lx; nc = n.lz; }
 	else { ca = clz; cb = clx; cc = cly; na = n.lz; nb = n.lx; nc = n.ly; }
 	const double min_area = fmin(cb * cc, nb * nc);
-	const double v = (ca * n.v + na * cv_a) / (ca + na);
+	const double num = ca * n.v + na * cv_a;
+	const double v = P2 ? num * rinv : num / (ca + na);
 	return (v >= 0 ? cd : n.d) * dt * v * min_area;
 }
 
@@ -335,6 +353,15 @@ __device__ __forceinline__ uint32_t nb_one_row(uint32_t a) { return a == 2 ? 5u 
 // per other axis, and every operand that was the component - the own cell's,
 // a neighbor's, a boundary face's two - is uv.v[a], the same bits, so the
 // densities are bitwise the UM = 0 kernel's.  No arithmetic is skipped.
+//
+// P2 (Grid::LenTable::pow2 verified it on the host): every level's 2 l_a and
+// volume are powers of two whose reciprocals are normal doubles, and LT
+// carries them behind the lengths (kLenTabP2 doubles: 96 lengths, 96 times
+// 1 / (2 l_a), 32 times 1 / volume).  A face between two cells of one level
+// divides by l_a + l_a = 2 l_a and a cell by its volume: both multiply by the
+// table's reciprocal instead, which rounds the same real number, so the bits
+// are the quotient's for every numerator (inf, NaN payloads and subnormals
+// included).  A face between two levels (3 l_a: not a power of two) divides.
 struct AdvUV {
 	double v[3];
 };
@@ -353,7 +380,14 @@ __host__ __device__ constexpr uint32_t vel_live_axis(int um, uint32_t k) {
 	return a;
 }
 
-template <int MINW, bool REC, bool LEN, int UM = 0>
+// a block-uniform double out of the vector registers
+__device__ __forceinline__ double uniform_f64(double x) {
+	const long long b = __double_as_longlong(x);
+	const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(b)), hi = __builtin_amdgcn_readfirstlane(uint32_t(b >> 32));
+	return __longlong_as_double((long long)((uint64_t(hi) << 32) | lo));
+}
+
+template <int MINW, bool REC, bool LEN, int UM = 0, bool P2 = false>
 __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs P, double* __restrict__ rho_out,
                                                                          const RegTileMeta* __restrict__ meta,
                                                                          uint32_t ntiles, double dt,
@@ -364,6 +398,8 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 	constexpr bool LOWN = LEN && DCCRGX_LEN_OWN;
 	constexpr bool LREG = LOWN && !DCCRGX_LEN_LDS;  // the lengths stay in registers
 	static_assert(UM == 0 || (LREG && UM > 0 && UM < 8), "uniform components: the register-length kernel only");
+	static_assert(!P2 || LREG, "reciprocals: the register-length kernel only");
+	constexpr uint32_t NLT = P2 ? kLenTabP2 : 96u;
 	constexpr int NV = 3 - __builtin_popcount(unsigned(UM));  // velocity components with a row
 	// rows rho, vx, vy, vz, lx, ly, lz; columns 0..511 the tile's own cells,
 	// 512 + 64 d + (face cell) the out-of-tile neighbor across side d (only
@@ -375,13 +411,13 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 	__shared__ double shd[NROW][W];
 	__shared__ double shg[3][512];  // flux through each cell's +x, +y, +z face
 	__shared__ double shm[3][64];   // flux through the tile's -x, -y, -z boundary faces
-	__shared__ double lt[LEN ? 96 : 1];  // LEN: the per-level lengths
+	__shared__ double lt[LEN ? NLT : 1];  // LEN: the per-level lengths (P2: and reciprocals)
 	const StaticTiles tk(ntiles);
 	const uint32_t t1 = tk.t1;
 	uint32_t t = tk.first();
 	if (t >= t1) return;  // block-uniform
 	const uint32_t tid = threadIdx.x;
-	if (LEN && tid < 96u) lt[tid] = LT[tid];  // (read after the first tile's first barrier)
+	if (LEN && tid < NLT) lt[tid] = LT[tid];  // (read after the first tile's first barrier)
 	const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63u;
 	const uint32_t l[3] = {(tid & 1u) | ((tid >> 2) & 2u) | ((tid >> 4) & 4u),
 	                       ((tid >> 1) & 1u) | ((tid >> 3) & 2u) | ((tid >> 5) & 4u),
@@ -469,14 +505,20 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 		}
 	};
 	// LEN: a tile's lengths, block-uniform (lt: after the first barrier)
+	// (P2: and 1 / (2 l_a), 1 / volume, kept in scalar registers)
 	struct TL {
-		double v[3];
+		double v[3], r[3], rv;
 	};
 	auto lengths = [&](const RM& m) {
-		TL tl{{0, 0, 0}};
+		TL tl{{0, 0, 0}, {0, 0, 0}, 0};
 		if (LEN) {
 			const uint32_t lv = 3u * m.lvl();
 			tl.v[0] = lt[lv]; tl.v[1] = lt[lv + 1]; tl.v[2] = lt[lv + 2];
+			if (P2) {
+#pragma unroll
+				for (int a = 0; a < 3; a++) tl.r[a] = uniform_f64(lt[96u + lv + uint32_t(a)]);
+				tl.rv = uniform_f64(lt[192u + m.lvl()]);
+			}
 		}
 		return tl;
 	};
@@ -533,8 +575,9 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 #pragma unroll
 		for (int a = 0; a < 3; a++) {
 			const uint32_t li = lp[a];
-			const double g = adv_face_g(a, cd, clx, cly, clz, cva[a],
-			                            AdvNb{shd[0][li], lrow(tl, 4, li), lrow(tl, 5, li), lrow(tl, 6, li), vel(a, li)}, dt);
+			const double g = adv_face_g<P2>(a, cd, clx, cly, clz, cva[a],
+			                                AdvNb{shd[0][li], lrow(tl, 4, li), lrow(tl, 5, li), lrow(tl, 6, li), vel(a, li)}, dt,
+			                                tl.r[a]);
 			const bool has = l[a] < 7 || mc.nst(2 * a + 1) >= 0;
 			shg[a][tid] = has ? g : 0.0;
 		}
@@ -546,9 +589,9 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 			const AdvNb self{shd[0][bcell], lrow(tl, 4, bcell), lrow(tl, 5, bcell), lrow(tl, 6, bcell), sv};
 			const double kx = lrow(tl, 4, k), ky = lrow(tl, 5, k), kz = lrow(tl, 6, k);
 			double gmv;
-			if (w == 0) gmv = adv_face_g(0, shd[0][k], kx, ky, kz, vel(0, k), self, dt);
-			else if (w == 1) gmv = adv_face_g(1, shd[0][k], kx, ky, kz, vel(1, k), self, dt);
-			else gmv = adv_face_g(2, shd[0][k], kx, ky, kz, vel(2, k), self, dt);
+			if (w == 0) gmv = adv_face_g<P2>(0, shd[0][k], kx, ky, kz, vel(0, k), self, dt, tl.r[0]);
+			else if (w == 1) gmv = adv_face_g<P2>(1, shd[0][k], kx, ky, kz, vel(1, k), self, dt, tl.r[1]);
+			else gmv = adv_face_g<P2>(2, shd[0][k], kx, ky, kz, vel(2, k), self, dt, tl.r[2]);
 			shm[w][lane] = gmv;
 		}
 		__syncthreads();
@@ -564,7 +607,7 @@ __global__ __launch_bounds__(512, MINW) void advection_regular_pp_kernel(AdvPtrs
 			acc += gm;
 			acc += -shg[a][tid];
 		}
-		st_nt(rho_out, ts + tid, cd + acc / (clx * cly * clz));
+		st_nt(rho_out, ts + tid, cd + (P2 ? acc * tl.rv : acc / (clx * cly * clz)));
 	};
 	RegSet ra;
 	RM cur = unpack(tile_record_word(meta, t, lane));
@@ -624,7 +667,15 @@ struct TileMeta {
 // per-tile addresses are recomputed per tile (`ti`).  The same length bits
 // reach the same operands, so the densities are bitwise the fields'.
 // DCCRGX_LEN_LDS_GEN=1 or DCCRGX_LEN_OWN=0 keep the seven rows and two blocks.
-template <int MINW, bool REC, bool LEN, int UM = 0>
+//
+// P2 (see advection_regular_pp_kernel): a face whose neighbor column's level
+// byte is the cell's own takes the neighbor's lengths from the own registers
+// (the same row, the same bits) and multiplies by the own level's
+// 1 / (2 l_a); a face to another level and the four fluxes of a finer face
+// divide as before, under a branch a wave skips when none of its lanes has
+// one.  The faces are still summed in the order -x .. +z, and the cell
+// multiplies by its level's 1 / volume.
+template <int MINW, bool REC, bool LEN, int UM = 0, bool P2 = false>
 __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
     AdvPtrs P, double* __restrict__ rho_out, const uint32_t* __restrict__ tell, uint32_t tplane,
     const uint32_t* __restrict__ ext, const uint32_t* __restrict__ tfine, const TileMeta* __restrict__ meta,
@@ -635,18 +686,21 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 	constexpr bool LOWN = LEN && DCCRGX_LEN_OWN;
 	constexpr bool LLVL = LOWN && !DCCRGX_LEN_LDS_GEN;  // no length rows: a level byte per column
 	static_assert(UM == 0 || (LLVL && UM > 0 && UM < 8), "uniform components: the level-row kernel only");
+	static_assert(!P2 || LLVL, "reciprocals: the level-row kernel only");
+	constexpr uint32_t NLT = P2 ? kLenTabP2 : 96u;
 	constexpr uint32_t T = 512;
 	// UM (see advection_regular_pp_kernel): a uniform component has no row
 	// (the launch still sizes the LDS for four, adv_tiles_lds)
 	constexpr uint32_t NROW = LLVL ? 4u - uint32_t(__builtin_popcount(unsigned(UM))) : 7;
 	// [NROW][T + ecap] doubles (rho vx vy vz lx ly lz); 2 x T u32 finer-face
-	// pairs; LEN: 96 doubles, the per-level lengths; LLVL: T + ecap level bytes
+	// pairs; LEN: 96 doubles, the per-level lengths (P2: kLenTabP2, with the
+	// reciprocals); LLVL: T + ecap level bytes
 	// (adv_tiles_lds restates the size)
 	extern __shared__ double shd[];
 	const uint32_t W = T + ecap;
 	uint32_t* shf = reinterpret_cast<uint32_t*>(shd + NROW * W);
 	double* lt = reinterpret_cast<double*>(shf + 2 * T);  // (LEN)
-	uint8_t* shl = reinterpret_cast<uint8_t*>(lt + 96);   // (LLVL)
+	uint8_t* shl = reinterpret_cast<uint8_t*>(lt + NLT);  // (LLVL)
 	const StaticTiles tk(ntiles);
 	const uint32_t t1 = tk.t1;
 	uint32_t t = tk.first();
@@ -670,7 +724,7 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 	double c[7], xa[7], xb[7];
 	uint32_t row[3], fq[2];
 	uint32_t lvc = 0, lva = 0, lvb = 0;  // LEN: the level bytes of c, xa, xb
-	if (LEN && tid < 96u) lt[tid] = LT[tid];  // (read after the first tile's first barrier)
+	if (LEN && tid < NLT) lt[tid] = LT[tid];  // (read after the first tile's first barrier)
 	auto load7 = [&](uint32_t slot, double (&v)[7]) {
 		const uint32_t o = slot << 3;
 		v[0] = ldo(rho, o);
@@ -821,6 +875,7 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 		}
 		const bool own = tid < n;
 		double cd = 0, cvx = 0, cvy = 0, cvz = 0, clx = 1, cly = 1, clz = 1;
+		uint32_t olv = 0;  // P2: the own level
 		if (own) {
 			cd = shd[ti];
 			cvx = (UM & 1) ? uv.v[0] : shd[vel_row(UM, 0) * W + ti];
@@ -829,7 +884,8 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 			if (LLVL) {
 				// own lengths: the table row of the cell's level byte, kept in
 				// registers across the compute phase
-				const uint32_t k = 3u * (uint32_t(shl[ti]) & 31u);
+				olv = uint32_t(shl[ti]) & 31u;
+				const uint32_t k = 3u * olv;
 				clx = lt[k]; cly = lt[k + 1]; clz = lt[k + 2];
 			} else {
 				clx = shd[(4 % NROW) * W + ti];
@@ -854,7 +910,15 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 			for (int d = 0; d < 6; d++) {
 				const uint32_t code = (rr[d >> 1] >> (16 * (d & 1))) & 0xffffu;
 				if (code == 0xffffu) continue;
-				if (code & 0x8000u) {
+				if (P2 && !(code & 0x8000u) && (uint32_t(shl[code]) & 31u) == olv) {
+					// a same-level neighbor: its lengths are the own ones
+					const uint32_t a = uint32_t(d >> 1);
+					const double nv = ((UM >> a) & 1) ? uv.v[a] : shd[vel_row(UM, a) * W + code];
+					const double ri = lt[96u + 3u * olv + a];
+					if (a == 0) acc += adv_face_flux_same(d, cd, clx, cly, clz, cvx, shd[code], nv, ri, dt);
+					else if (a == 1) acc += adv_face_flux_same(d, cd, cly, clx, clz, cvy, shd[code], nv, ri, dt);
+					else acc += adv_face_flux_same(d, cd, clz, clx, cly, cvz, shd[code], nv, ri, dt);
+				} else if (code & 0x8000u) {
 					const uint32_t fk = code & 0x7fffu;
 					const uint32_t q0 = shf[2 * fk], q1 = shf[2 * fk + 1];
 					const uint32_t li[4] = {q0 & 0xffffu, q0 >> 16, q1 & 0xffffu, q1 >> 16};
@@ -865,7 +929,7 @@ __global__ __launch_bounds__(512, MINW) void advection_tiles_pp_kernel(
 					acc += adv_face_flux_d(d, cd, clx, cly, clz, cvx, cvy, cvz, fetch(code, d), dt);
 				}
 			}
-			st_nt(rho_out, ts + ti, cd + acc / (clx * cly * clz));
+			st_nt(rho_out, ts + ti, cd + (P2 ? acc * lt[192u + olv] : acc / (clx * cly * clz)));
 		}
 		if (!more) break;
 		cur = nxt;
@@ -911,11 +975,11 @@ constexpr int kRegWaves = 2 * DCCRGX_REG_BLOCKS, kGenWaves = 2 * DCCRGX_GEN_BLOC
 constexpr bool kLvlRow = DCCRGX_LEN_OWN && !DCCRGX_LEN_LDS_GEN;
 
 // dynamic LDS of advection_tiles_pp_kernel (restates the kernel's layout)
-static size_t adv_tiles_lds(uint32_t ecap, bool len) {
+static size_t adv_tiles_lds(uint32_t ecap, bool len, bool pow2) {
 	const size_t W = size_t(512) + ecap;
 	const bool lvl_row = len && kLvlRow;
 	return (lvl_row ? 4 : 7) * W * sizeof(double) + size_t(2) * 512 * sizeof(uint32_t) +
-	       (len ? 96 * sizeof(double) : 0) + (lvl_row ? (W + 7) / 8 * 8 : 0);
+	       (len ? (pow2 ? kLenTabP2 : 96) * sizeof(double) : 0) + (lvl_row ? (W + 7) / 8 * 8 : 0);
 }
 
 // The length-table kernels' instantiation for the mask of uniform velocity
@@ -946,8 +1010,10 @@ using GenKernel = void (*)(AdvPtrs, double*, const uint32_t*, uint32_t, const ui
 static RegKernel adv_regular_kernel(const AdvSweepPlan& p) {
 	if (p.rec) return advection_regular_pp_kernel<4, true, false>;
 	if (p.len)
-		return with_vel_mask(p.um[0], [](auto M) -> RegKernel {
-			return advection_regular_pp_kernel<kRegWaves, false, true, kRegMasks ? decltype(M)::value : 0>;
+		return with_vel_mask(p.um[0], [&](auto M) -> RegKernel {
+			constexpr int um = kRegMasks ? decltype(M)::value : 0;
+			return p.pow2 ? advection_regular_pp_kernel<kRegWaves, false, true, um, kRegMasks>
+			              : advection_regular_pp_kernel<kRegWaves, false, true, um>;
 		});
 	return advection_regular_pp_kernel<4, false, false>;
 }
@@ -955,8 +1021,16 @@ static RegKernel adv_regular_kernel(const AdvSweepPlan& p) {
 static GenKernel adv_general_kernel(const AdvSweepPlan& p) {
 	if (p.rec) return advection_tiles_pp_kernel<4, true, false>;
 	if (p.len)
-		return with_vel_mask(p.um[1], [](auto M) -> GenKernel {
-			return advection_tiles_pp_kernel<kGenWaves, false, true, kGenMasks ? decltype(M)::value : 0>;
+		return with_vel_mask(p.um[1], [&](auto M) -> GenKernel {
+			constexpr int um = kGenMasks ? decltype(M)::value : 0;
+			// the dividing kernels of the masks with vy or vz uniform come out
+			// at seven waves per SIMD in the three-block build; left to the
+			// bound of six the reciprocal ones take 73-77 registers, so they
+			// are compiled for seven (no scratch) and none has fewer waves
+			// than the dividing kernel of its mask
+			constexpr int w = kGenWaves + (kGenWaves == 6 && um >= 2 ? 1 : 0);
+			return p.pow2 ? advection_tiles_pp_kernel<w, false, true, um, kGenMasks>
+			              : advection_tiles_pp_kernel<kGenWaves, false, true, um>;
 		});
 	return advection_tiles_pp_kernel<4, false, false>;
 }
@@ -973,7 +1047,7 @@ const Grid::SweepLaunch& adv_sweep_launch(Grid& g, int kind, const AdvSweepPlan&
 	} else {
 		fn = reinterpret_cast<void*>(adv_general_kernel(plan));
 		table = plan.len != nullptr;
-		lds_min = adv_tiles_lds(uint32_t(g.max_ext), table);
+		lds_min = adv_tiles_lds(uint32_t(g.max_ext), table, table && plan.pow2);
 		if (table) cap = DCCRGX_GEN_BLOCKS;
 	}
 	Grid::SweepLaunch& L = g.adv_launch[kind];

@@ -1642,6 +1642,14 @@ int dccrgx_advection_velocity_source(dccrgx_grid* gp, const int fids[7], int* ma
 	});
 }
 
+int dccrgx_advection_divide_source(dccrgx_grid* gp, const int fids[7], int* out) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		advection_divide_source(g, fids, out);
+		return 0;
+	});
+}
+
 int dccrgx_advection_commit(dccrgx_grid* gp, int df) {
 	return guard([&] {
 		GRID_OR_FAIL(gp);

@@ -95,6 +95,7 @@ void advection_layout(Grid& g, uint64_t out[12]);
 void advection_occupancy(Grid& g, uint64_t out[6]);
 void advection_length_source(Grid& g, const int fids[7], int* out);
 void advection_velocity_source(Grid& g, const int fids[7], int* mask);
+void advection_divide_source(Grid& g, const int fids[7], int* out);
 void advection_commit(Grid& g, int df);
 void advection_initialize(Grid& g, const int fids[7]);
 void advection_max_time_step(Grid& g, const int fids[7], double* out);

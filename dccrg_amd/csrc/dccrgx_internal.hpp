@@ -865,9 +865,13 @@ struct Grid {
 	// lengths bitwise with its level's row, for the key below (tiles, slots,
 	// level-0 lengths, the three fields' ids / write epochs / arrays).
 	struct LenTable {
-		DBuf<double> tab;  // 32 rows of (lx, ly, lz)
+		DBuf<double> tab;  // 32 rows of (lx, ly, lz), then the reciprocals (kLenTabP2)
 		DBuf<int> flag;
 		double tab_l0[3] = {0, 0, 0};  // the level-0 lengths `tab` holds
+		// every level's 2 l_a and volume are powers of two with normal
+		// reciprocals (decided on the host when `tab` is filled): the sweeps
+		// may multiply by tab's reciprocals instead of dividing
+		bool pow2 = false;
 		FieldKey<3> key;
 		uint64_t tiles_gen = 0;
 		size_t n_slots = 0;
@@ -1194,8 +1198,8 @@ void k_gather_rows(const uint8_t* old_data, const int32_t* src, size_t n, size_t
 
 // --- launchers implemented in advection_sweep.hip; the caches and the plan --
 // --- of the sweep they serve (ensure_*, adv_sweep_plan) are advection.hip's -
-// the per-level length table (32 rows of lx, ly, lz) for the sweep of fields
-// fids when every slot's three lengths are bitwise their level's row, checked
+// the per-level length table (32 rows of lx, ly, lz, then their reciprocals:
+// kLenTabP2 doubles) for the sweep of fields fids when every slot's three lengths are bitwise their level's row, checked
 // by one device pass and cached (Grid::LenTable); nullptr - the sweeps read
 // the length fields - otherwise, when a length field is external, a stretched
 // geometry is held, DCCRGX_LEN_TABLE=0 or DCCRGX_NBREC=1 (advection.hip).
@@ -1262,12 +1266,19 @@ constexpr bool kRegMasks = DCCRGX_LEN_OWN && !DCCRGX_LEN_LDS, kGenMasks = DCCRGX
 // length table (never both, nullptr: the kernels read the fields), and per
 // kind of tile (0 regular, 1 other) the mask of uniform velocity components,
 // whose values are uv.  The kernels and their launch follow from it alone.
+// pow2: the length-table kernels multiply by the table's reciprocals where the
+// divisor is a power of two (Grid::LenTable::pow2; `len` then holds kLenTabP2
+// doubles).
 struct AdvSweepPlan {
 	const double* rec = nullptr;
 	const double* len = nullptr;
 	int um[2] = {0, 0};
 	double uv[3] = {0, 0, 0};
+	bool pow2 = false;
 };
+// the length table with its reciprocals: 32 rows of (lx, ly, lz), 32 rows of
+// 1 / (2 lx), 1 / (2 ly), 1 / (2 lz), then 1 / (lx ly lz) of the 32 levels
+constexpr uint32_t kLenTabP2 = 96 + 96 + 32;
 // sweep: the call precedes a sweep (ensure_len_table, ensure_vel_uniform)
 AdvSweepPlan adv_sweep_plan(Grid& g, const int fids[7], bool sweep);
 // tiled advection sweep over the regular and the irregular tiles of one run

@@ -1250,6 +1250,14 @@ class Dccrg:
         check(lib().dccrgx_advection_velocity_source(self.h, self._fids(fields), C.byref(v)))
         return v.value
 
+    def advection_divide_source(self, fields):
+        """1 when the tile sweeps of `fields` multiply by a reciprocal where the
+        divisor is a power of two (a face between two cells of one level, the
+        cell volume), 0 when they divide everywhere (see include/dccrgx.h)."""
+        v = C.c_int()
+        check(lib().dccrgx_advection_divide_source(self.h, self._fids(fields), C.byref(v)))
+        return v.value
+
     def advection_layout(self):
         """Tile layout of the advection sweep and its algorithmic HBM bytes per
         sweep over all local cells (see include/dccrgx.h)."""

@@ -937,6 +937,21 @@ int dccrgx_advection_length_source(dccrgx_grid* g, const int fids[7], int* out);
  * bitwise the same either way.  No reference counterpart. */
 int dccrgx_advection_velocity_source(dccrgx_grid* g, const int fids[7], int* mask);
 
+/* Whether the tile sweeps of fields fids divide or multiply where the divisor
+ * is a power of two: *out = 1 - a face between two cells of one level
+ * multiplies its velocity sum by 1 / (2 l_a) and a cell its flux sum by
+ * 1 / (lx ly lz), both from the per-level table; a face between two levels
+ * still divides.  That needs the table (dccrgx_advection_length_source is 1)
+ * and level-0 cell lengths that are powers of two on all three axes such that
+ * at each of the 32 levels the length, 2 l_a, the volume and their
+ * reciprocals are normal doubles: decided on the host when the table is
+ * filled, one verdict for the three axes.  0: the sweeps divide everywhere
+ * (some axis fails, no table, or DCCRGX_DIV_POW2=0).  A product with an exact
+ * reciprocal rounds the real number the quotient rounds, so the densities are
+ * bitwise the same either way.  dccrgx_advection_layout's byte counts do not
+ * depend on it.  No reference counterpart. */
+int dccrgx_advection_divide_source(dccrgx_grid* g, const int fids[7], int* out);
+
 /* ---- Poisson solver (tests/poisson/poisson_solve.hpp:156-1056) ----------
  * dccrgx_poisson_cache = Poisson_Solve::cache_system_info (827-971): local
  * cells default to boundary cells, ids in skip_cells are skipped, ids in
