@@ -12,11 +12,12 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libdccrgx.so")
-SOURCES = ["api.hip", "grid.hip", "mesh.hip", "comm.hip", "partition.hip", "build_kernels.hip", "tile_build.hip", "payload.hip",
+SOURCES = ["api.hip", "grid.hip", "mesh.hip", "comm.hip", "partition.hip", "device_prims.hip", "mesh_table.hip",
+           "neighbor_build.hip", "halo_lists.hip", "face_build.hip", "mesh_refine.hip", "tile_build.hip", "payload.hip",
            "gol.hip", "gol_amr.hip", "advection.hip", "advection_sweep.hip", "advection_adapt.hip", "poisson.hip", "poisson_kernels.hip",
            "varfield.hip", "particles.hip", "geometry.hip", "pool.hip", "field_adapt.hip", "grid_file.hip", "field_ops.hip"]
 HEADERS = ["dccrgx_internal.hpp", "dccrgx_grid.hpp", "dccrgx_mapping.hpp", "dccrgx_mesh.hpp", "dccrgx_neighbors.hpp",
-           "dccrgx_reduce.hpp", "dccrgx_stencil.hpp", "dccrgx_philox.hpp"]
+           "dccrgx_reduce.hpp", "dccrgx_stencil.hpp", "dccrgx_philox.hpp", "dccrgx_prims.hpp", "dccrgx_wave.hpp"]
 ARCH = os.environ.get("DCCRGX_ARCH", "gfx950")
 
 

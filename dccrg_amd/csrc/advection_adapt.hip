@@ -393,10 +393,8 @@ void k_min_partials(const double* partial, size_t n, double* out, hipStream_t s)
 void k_adv_bands(const MapCtx& m, const double* rho, const FaceView& F, const uint8_t* lvl8, size_t n,
                  double diff_increase, double diff_threshold, double unrefine_sensitivity, uint8_t* band,
                  hipStream_t s) {
-	if (!n) return;
-	adv_bands_kernel<<<grid_for(n, 256), 256, 0, s>>>(m, rho, F.ell, F.fine, lvl8, F.slot_ids, n, diff_increase,
-	                                                  diff_threshold, unrefine_sensitivity, band);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(adv_bands_kernel, n, s, m, rho, F.ell, F.fine, lvl8, F.slot_ids, n, diff_increase,
+	                diff_threshold, unrefine_sensitivity, band);
 }
 
 // adapt_grid's merged parents (adapter.hpp:260-290) from the removed store's
@@ -517,15 +515,11 @@ size_t k_adv_reset(const MapCtx& m, const uint64_t* slot_ids, size_t n, const do
 size_t k_adv_candidates(const MapCtx& m, const double* rho, const FaceView& F, const uint8_t* lvl8, size_t n,
                         double diff_increase, double diff_threshold, uint64_t* out, hipStream_t s) {
 	if (!n) return 0;
-	DBuf<unsigned long long> ctr;
-	ctr.alloc(1);
-	HIP_CHECK(hipMemsetAsync(ctr.p, 0, sizeof(unsigned long long), s));
+	DevCounter ctr;
 	adv_candidates_kernel<<<grid_for(n, 256), 256, 0, s>>>(m, rho, F.ell, F.fine, lvl8, F.slot_ids, n, diff_increase,
-	                                                       diff_threshold, out, ctr.p);
+	                                                       diff_threshold, out, ctr.zero(s));
 	HIP_CHECK(hipGetLastError());
-	unsigned long long h = 0;
-	d2h_small(&h, ctr.p, sizeof(h), s);
-	return size_t(h);
+	return ctr.read(s);
 }
 
 }  // namespace dccrgx

@@ -1188,9 +1188,7 @@ void k_ext_axis_count(const uint32_t* tmeta, size_t ntiles, const uint32_t* ext_
 }
 
 void k_nbrec(const double* const f[7], size_t n, double* r, hipStream_t s) {
-	if (!n) return;
-	nbrec_kernel<<<grid_for(n, 256), 256, 0, s>>>(f[4], f[5], f[6], f[1], f[2], f[3], n, r);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(nbrec_kernel, n, s, f[4], f[5], f[6], f[1], f[2], f[3], n, r);
 }
 
 

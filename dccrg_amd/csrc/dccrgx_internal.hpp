@@ -254,7 +254,11 @@ inline std::vector<T> download(const T* d, size_t n, hipStream_t s) {
 	return h;
 }
 
-void sort_u64(uint64_t* keys, size_t n, hipStream_t s, int end_bit);  // (declared with its default below)
+}  // namespace dccrgx
+
+#include "dccrgx_prims.hpp"
+
+namespace dccrgx {
 
 inline const std::vector<uint64_t>& LazyIds::host(hipStream_t s) {
 	if (!host_valid) {
@@ -296,6 +300,15 @@ inline unsigned grid_for(size_t n, unsigned per_block, unsigned cap = 256u * 32u
 	if (g == 0) g = 1;
 	return unsigned(g);
 }
+#if defined(__HIPCC__)
+// the launch of a kernel over n items: none for n == 0, else blocks of 256 on s
+template <class... P, class... A>
+inline void launch_per_item(void (*kernel)(P...), size_t n, hipStream_t s, A... args) {
+	if (!n) return;
+	kernel<<<grid_for(n, 256), 256, 0, s>>>(args...);
+	HIP_CHECK(hipGetLastError());
+}
+#endif
 
 // XCD-contiguous block order: hardware block b runs on XCD b % 8, so XCD x
 // sweeps the contiguous x-th eighth of the logical blocks and the neighbor
@@ -990,10 +1003,6 @@ void mesh_from_local(Grid& g, Mesh& out, DBuf<uint64_t>& local, size_t n_local);
 // (entries i < slot_upto get slot i, the others -1)
 void mesh_build_range(Grid& g, Mesh& M, const uint64_t* ids, const int32_t* owners, size_t n, hipStream_t s,
                       size_t slot_upto);
-bool k_level_ranges(const MapCtx& m, const uint64_t* ids, size_t n, uint64_t* lo, uint64_t* hi, hipStream_t s);
-void k_range_insert(int2* rmap, const DevMesh& M, const uint64_t* ids, const int32_t* owners, size_t n, size_t slot_upto,
-                    hipStream_t s);
-void k_range_clear(int2* rmap, const DevMesh& M, const uint64_t* ids, size_t n, hipStream_t s);
 void mesh_build_hash(Mesh& M, const uint64_t* ids, const int32_t* owners, size_t n, hipStream_t s,
                      size_t slot_upto = 0);
 void rebuild(Grid& g, Mesh& new_mesh);  // new_mesh is moved into g.mesh
@@ -1022,13 +1031,24 @@ struct FaceView {
 	size_t n_local;
 };
 
-// --- launchers implemented in build_kernels.hip -----------------------------
-void k_fill_i32(int32_t* p, size_t n, int32_t v, hipStream_t s);
-void k_iota_u64(uint64_t* out, uint64_t first, size_t n, hipStream_t s);
+// --- launchers implemented in mesh_table.hip --------------------------------
+bool k_level_ranges(const MapCtx& m, const uint64_t* ids, size_t n, uint64_t* lo, uint64_t* hi, hipStream_t s);
+void k_range_insert(int2* rmap, const DevMesh& M, const uint64_t* ids, const int32_t* owners, size_t n, size_t slot_upto,
+                    hipStream_t s);
+void k_range_clear(int2* rmap, const DevMesh& M, const uint64_t* ids, size_t n, hipStream_t s);
 void k_hash_insert(HashEntry* tab, uint64_t mask, uint32_t shift, const uint64_t* ids, const int32_t* owners,
                    int32_t owner_const, size_t n, hipStream_t s, size_t slot_upto = 0);
 void k_hash_set_slots(const DevMesh& M, const uint64_t* slot_ids, size_t n, int32_t* err, hipStream_t s);
 void k_lookup(const DevMesh& M, const uint64_t* ids, size_t n, int32_t* owner, int32_t* slot, hipStream_t s);
+void k_lookup_slots(const uint64_t* ids, size_t n, const DevMesh& M, int32_t* out, int32_t* err_flag, hipStream_t s);
+// (id, slot) of every slot sorted by id
+void k_sorted_slot_index(const uint64_t* slot_ids, size_t n, std::vector<uint64_t>& ids, std::vector<int32_t>& slots,
+                         hipStream_t s);
+void k_carry_src(const uint64_t* slot_ids, size_t n_slots, size_t nl, const MapCtx& m, const DevMesh& oldM,
+                 size_t old_n_local, int32_t* src, hipStream_t s);
+void k_slot_levels(const MapCtx& m, const uint64_t* slot_ids, size_t n, uint8_t* lvl, hipStream_t s);
+
+// --- launchers implemented in neighbor_build.hip ----------------------------
 // flag local cells that have a remote neighbors_of / neighbors_to entry;
 // with `near` (a byte per level-0 id in [near_lo, near_lo + near_n), see
 // k_level0_near) only cells whose level-0 parent is marked are examined, the
@@ -1055,9 +1075,23 @@ void k_count_rows(const MapCtx& m, const int32_t* hood, const int32_t* hood_to, 
                   const uint64_t* slot_ids, size_t row0, size_t nrows, uint32_t* nof_cnt, uint32_t* nto_cnt,
                   hipStream_t s);
 int max_hood_items();  // largest stencil the neighbors_to dedupe can hold in LDS
-// the entries of an id array owned by another process, grouped by owner
-// (each group ascending, unique); device sorts of owner * (last + 1) + id
-// keys, or of (owner, id) pairs when the ids leave no room for the owner
+// iterator ranges cell.neighbors_of (update_cell_pointers 11451-11500): pass
+// 0 classifies the neighbors_of entries into cls (one byte per entry) and
+// counts, pass 1 fills slots (+ offsets when it_off != nullptr)
+void k_iterator_lists(const uint32_t* nof_ptr, const uint64_t* nof_id, const int32_t* nof_off,
+                      const int32_t* nof_slot, const uint32_t* nto_ptr, const uint64_t* nto_id, size_t nrows,
+                      uint8_t* cls, uint32_t* it_cnt, const uint32_t* it_ptr, int32_t* it_slot, int32_t* it_off,
+                      int pass, hipStream_t s);
+// refinement closure (induce_refines 9591-9720): coarser neighbors_of /
+// neighbors_to entries of the requested local cells; finer: the finer ones
+// (the dont_refine spread of override_refines 9991-10038)
+std::vector<uint64_t> k_induced_refines(const MapCtx& m, const int32_t* hood, const int32_t* hood_to, int nh,
+                                        const DevMesh& M, int rank, const std::vector<uint64_t>& req, hipStream_t s,
+                                        bool finer = false, const uint64_t* dreq_given = nullptr);
+
+// --- launchers implemented in halo_lists.hip --------------------------------
+// (device sorts of owner * (last + 1) + id keys, or of (owner, id) pairs when
+// the ids leave no room for the owner)
 // remote ids of `ids` grouped by owner, each group ascending; `keep` (when
 // given) receives the sorted unique (owner * (last + 1) + id) keys on the
 // device and `keep_n` their count (0 and no keys when the keys would overflow)
@@ -1077,7 +1111,6 @@ struct HaloLists {
 bool k_halo_lists(const uint64_t* of_id, size_t t_of, const uint64_t* to_id, const uint32_t* p_to, size_t t_to,
                   const uint64_t* slot_ids, size_t row0, size_t nrows, const DevMesh& M, int rank, int size,
                   HaloLists& out, hipStream_t s);
-void k_iota_i32(int32_t* out, size_t n, int32_t first, hipStream_t s);
 // the remote ids of `ids` whose key is not among `of_keys` (kept by
 // k_remote_by_owner), ascending; false when keys would overflow
 bool k_remote_extra(const uint64_t* ids, size_t n, const DevMesh& M, int rank, int size, const uint64_t* of_keys,
@@ -1087,30 +1120,10 @@ bool k_remote_extra(const uint64_t* ids, size_t n, const DevMesh& M, int rank, i
 void k_send_by_owner(const uint64_t* nto_id, const uint32_t* nto_ptr, size_t n_entries, const uint64_t* slot_ids,
                      size_t row0, size_t nrows, const DevMesh& M, int rank, int size,
                      std::map<int, std::vector<uint64_t>>& out, hipStream_t s);
-size_t sort_unique_u64(uint64_t* keys, size_t n, hipStream_t s, int end_bit = 64);  // in place; keys < 2^end_bit
-void sort_u64(uint64_t* keys, size_t n, hipStream_t s, int end_bit = 64);  // in place; keys < 2^end_bit
-void host_sort_u64(std::vector<uint64_t>& v, bool unique, hipStream_t s);  // host list, device radix sort when large
-// (id, slot) of every slot sorted by id
-void k_sorted_slot_index(const uint64_t* slot_ids, size_t n, std::vector<uint64_t>& ids, std::vector<int32_t>& slots,
-                         hipStream_t s);
+
+// --- launchers implemented in face_build.hip --------------------------------
 void k_morton_merge2(const MapCtx& m, uint64_t* ids, size_t n, size_t run1, hipStream_t s);
 void k_morton_sort(const MapCtx& m, uint64_t* ids, size_t n, hipStream_t s);
-uint32_t scan_exclusive_u32(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);  // returns total
-// two scans of n + 1 entries (the same temp storage size), both totals in one read
-void scan_exclusive_u32_pair(const uint32_t* in1, uint32_t* out1, const uint32_t* in2, uint32_t* out2, size_t n,
-                             hipStream_t s, size_t& t1, size_t& t2);
-// the same, and out[at[j]] (j < k <= 3) into vals, all in one device read
-uint32_t scan_exclusive_u32_at(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s, const size_t* at, int k,
-                               uint32_t* vals);
-void k_lookup_slots(const uint64_t* ids, size_t n, const DevMesh& M, int32_t* out, int32_t* err_flag, hipStream_t s);
-// iterator ranges cell.neighbors_of (update_cell_pointers 11451-11500): pass
-// 0 classifies the neighbors_of entries into cls (one byte per entry) and
-// counts, pass 1 fills slots (+ offsets when it_off != nullptr)
-void k_iterator_lists(const uint32_t* nof_ptr, const uint64_t* nof_id, const int32_t* nof_off,
-                      const int32_t* nof_slot, const uint32_t* nto_ptr, const uint64_t* nto_id, size_t nrows,
-                      uint8_t* cls, uint32_t* it_cnt, const uint32_t* it_ptr, int32_t* it_slot, int32_t* it_off,
-                      int pass, hipStream_t s);
-void k_slot_levels(const MapCtx& m, const uint64_t* slot_ids, size_t n, uint8_t* lvl, hipStream_t s);
 // the fixed-width face table of rows [0, nrows) (ensure_face); fine is
 // allocated here; returns the number of finer faces
 size_t k_face_table(const MapCtx& m, const DevMesh& M, const uint64_t* slot_ids, size_t nrows, size_t run1,
@@ -1118,8 +1131,8 @@ size_t k_face_table(const MapCtx& m, const DevMesh& M, const uint64_t* slot_ids,
 // its CSR rows (ensure_face_csr)
 void k_face_csr(const int32_t* ell, const int32_t* fine, size_t nrows, DBuf<uint32_t>& ptr, DBuf<int32_t>& ent,
                 hipStream_t s);
-void k_carry_src(const uint64_t* slot_ids, size_t n_slots, size_t nl, const MapCtx& m, const DevMesh& oldM,
-                 size_t old_n_local, int32_t* src, hipStream_t s);
+
+// --- launchers implemented in mesh_refine.hip -------------------------------
 // ghost region: the level-0 cells within `radius` of the level-0 parent of a
 // local cell that are not wholly owned here (sorted, unique)
 std::vector<uint64_t> k_ghost_level0(const MapCtx& m, const DevMesh& M, int rank, const uint64_t* local, size_t n,
@@ -1127,12 +1140,6 @@ std::vector<uint64_t> k_ghost_level0(const MapCtx& m, const DevMesh& M, int rank
 // local cells whose level-0 parent is in `l0` (sorted)
 std::vector<uint64_t> k_cells_under(const MapCtx& m, const uint64_t* local, size_t n, const std::vector<uint64_t>& l0,
                                     hipStream_t s);
-// refinement closure (induce_refines 9591-9720): coarser neighbors_of /
-// neighbors_to entries of the requested local cells; finer: the finer ones
-// (the dont_refine spread of override_refines 9991-10038)
-std::vector<uint64_t> k_induced_refines(const MapCtx& m, const int32_t* hood, const int32_t* hood_to, int nh,
-                                        const DevMesh& M, int rank, const std::vector<uint64_t>& req, hipStream_t s,
-                                        bool finer = false, const uint64_t* dreq_given = nullptr);
 // override_unrefines (9796-9898) on the device: the requested cells'
 // parents (sorted, unique) whose families may merge given the final refine
 // set S (sorted): none of the children refined or marked dont_unrefine (DU,
@@ -1372,7 +1379,6 @@ void k_time_begin(Grid& g);
 void k_time_end(Grid& g);
 
 // --- variable-size fields (varfield.hip) ----------------------------------
-uint64_t scan_exclusive_u64(const uint64_t* in, uint64_t* out, size_t n, hipStream_t s);  // returns total
 void var_reset(Field& f, size_t n_slots, hipStream_t s);  // every slot empty
 uint64_t var_total(const Field& f, size_t n_slots, hipStream_t s);
 // sizes of slots[i] (slots != nullptr) or of slot0 + i, into out (device)

@@ -27,7 +27,6 @@
 // neighbor rows are the device neighbors_of CSR (slots); the level-0 parent
 // of every slot is decoded once per call.  Integer work, latency bound
 // (a dependent gather per neighbor entry).
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstdlib>
@@ -947,30 +946,23 @@ void k_gol_amr_tables(const MapCtx& m, const uint64_t* slot_ids, size_t n_slots,
 	cnt.alloc(2);
 	HIP_CHECK(hipMemsetAsync(cnt.p, 0, 16, s));
 	if (n_slots) {
-		l0_table_kernel<<<grid_for(n_slots, 256), 256, 0, s>>>(m, slot_ids, n_slots, T.l0.p, keys.p, cnt.p);
-		HIP_CHECK(hipGetLastError());
-		size_t bytes = 0;
-		HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, keys.p, sorted.p, n_slots, 0, 64, s));
-		DBuf<uint8_t> temp;
-		temp.alloc(bytes + 1);
-		HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(temp.p, bytes, keys.p, sorted.p, n_slots, 0, 64, s));
+		launch_per_item(l0_table_kernel, n_slots, s, m, slot_ids, n_slots, T.l0.p, keys.p, cnt.p);
+		with_temp(cub_sort_keys(keys.p, sorted.p, n_slots, 64, s));
 	}
 	DBuf<uint32_t> head, pos;
 	head.alloc(n_slots + 1);
 	pos.alloc(n_slots + 1);
 	HIP_CHECK(hipMemsetAsync(head.p, 0, (n_slots + 1) * 4, s));
 	if (n_slots) {
-		group_heads_kernel<<<grid_for(n_slots, 256), 256, 0, s>>>(sorted.p, n_slots, head.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(group_heads_kernel, n_slots, s, sorted.p, n_slots, head.p);
 	}
 	const size_t ng = scan_exclusive_u32(head.p, pos.p, n_slots, s);
 	T.gptr.alloc(ng + 1);
 	T.gslot.alloc(n_slots + 1);
 	T.lvl0.alloc(n_local + 1);
 	if (n_slots) {
-		group_fill_kernel<<<grid_for(n_slots, 256), 256, 0, s>>>(sorted.p, n_slots, head.p, pos.p, T.gptr.p, T.gslot.p,
-		                                                        T.lvl0.p, cnt.p + 1, T.l0.p, n_local);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(group_fill_kernel, n_slots, s, sorted.p, n_slots, head.p, pos.p, T.gptr.p, T.gslot.p,
+		                T.lvl0.p, cnt.p + 1, T.l0.p, n_local);
 	}
 	unsigned long long h[2] = {0, 0};
 	d2h_small(h, cnt.p, 16, s);
@@ -1005,12 +997,10 @@ void k_gol_amr_tables(const MapCtx& m, const uint64_t* slot_ids, size_t n_slots,
 		bad.alloc(1);
 		HIP_CHECK(hipMemsetAsync(bad.p, 0, 4, s));
 		if (n_slots) {
-			mask_l0c_kernel<<<grid_for(n_slots, 256), 256, 0, s>>>(m, slot_ids, n_slots, G, T.l0c.p);
-			HIP_CHECK(hipGetLastError());
+			launch_per_item(mask_l0c_kernel, n_slots, s, m, slot_ids, n_slots, G, T.l0c.p);
 		}
 		if (n_local) {
-			mask_ent_kernel<<<grid_for(n_local, 256), 256, 0, s>>>(ptr, nslot, n_local, T.l0c.p, G, T.ent.p, bad.p);
-			HIP_CHECK(hipGetLastError());
+			launch_per_item(mask_ent_kernel, n_local, s, ptr, nslot, n_local, T.l0c.p, G, T.ent.p, bad.p);
 		}
 		int hb = 0;
 		d2h_small(&hb, bad.p, 4, s);
@@ -1065,8 +1055,7 @@ void k_gol_amr_tables(const MapCtx& m, const uint64_t* slot_ids, size_t n_slots,
 			HIP_CHECK(hipMemsetAsync(T.l0tab.p, 0, size_t(vol), s));
 			T.corner.alloc(n_local + 1);
 			if (n_local) {
-				geo_corner_kernel<<<grid_for(n_local, 256), 256, 0, s>>>(m, slot_ids, n_local, T.corner.p);
-				HIP_CHECK(hipGetLastError());
+				launch_per_item(geo_corner_kernel, n_local, s, m, slot_ids, n_local, T.corner.p);
 			}
 			// the level-0 game's layout (families as eight consecutive slots)
 			T.lg_layout = false;
@@ -1074,8 +1063,7 @@ void k_gol_amr_tables(const MapCtx& m, const uint64_t* slot_ids, size_t n_slots,
 				DBuf<int> bad;
 				bad.alloc(1);
 				HIP_CHECK(hipMemsetAsync(bad.p, 0, 4, s));
-				lg_layout_check_kernel<<<grid_for(n_local, 256), 256, 0, s>>>(T.corner.p, T.l0c.p, n_local, bad.p);
-				HIP_CHECK(hipGetLastError());
+				launch_per_item(lg_layout_check_kernel, n_local, s, T.corner.p, T.l0c.p, n_local, bad.p);
 				int hb = 1;
 				d2h_small(&hb, bad.p, 4, s);
 				T.lg_layout = hb == 0;
@@ -1084,12 +1072,10 @@ void k_gol_amr_tables(const MapCtx& m, const uint64_t* slot_ids, size_t n_slots,
 				DBuf<uint32_t> flag, pos;
 				flag.alloc(n_local + 1);
 				pos.alloc(n_local + 1);
-				lg_row_flags_kernel<<<grid_for(n_local, 256), 256, 0, s>>>(T.corner.p, n_local, flag.p);
-				HIP_CHECK(hipGetLastError());
+				launch_per_item(lg_row_flags_kernel, n_local, s, T.corner.p, n_local, flag.p);
 				T.n_lg_rows = scan_exclusive_u32(flag.p, pos.p, n_local, s);
 				T.lg_rows.alloc(T.n_lg_rows + 1);
-				lg_row_fill_kernel<<<grid_for(n_local, 256), 256, 0, s>>>(flag.p, pos.p, n_local, T.lg_rows.p);
-				HIP_CHECK(hipGetLastError());
+				launch_per_item(lg_row_fill_kernel, n_local, s, flag.p, pos.p, n_local, T.lg_rows.p);
 			}
 			HIP_CHECK(hipStreamSynchronize(s));
 			T.geo = true;
@@ -1115,8 +1101,7 @@ void k_gol_amr_geo(GolAmrTables& T, const int32_t* hood, int nh, const uint32_t*
 	               {T.geo_bstride[0], T.geo_bstride[1], T.geo_bstride[2]},
 	               {T.geo_istride[0], T.geo_istride[1], T.geo_istride[2]}};
 	if (n_state) {
-		geo_l0_leaves_kernel<<<grid_for(n_state, 256), 256, 0, s>>>(T.l0.p, T.l0c.p, state, n_state, G, B, T.l0tab.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(geo_l0_leaves_kernel, n_state, s, T.l0.p, T.l0c.p, state, n_state, G, B, T.l0tab.p);
 	}
 	if (T.ng) {
 		geo_l0_groups_kernel<<<xcd_grid((8 * T.ng + 255) / 256), 256, 0, s>>>(T.gptr.p, T.ng, T.gslot.p, T.l0c.p, state,
@@ -1199,8 +1184,7 @@ void k_gol_amr(int phase, GolAmrTables& T, size_t n_slots, size_t n_local, uint3
 		return;
 	}
 	if (phase == 0) {
-		gol_amr_pack_kernel<<<grid_for(n_slots, 256), 256, 0, s>>>(T.l0.p, state, n_slots, T.pack.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(gol_amr_pack_kernel, n_slots, s, T.l0.p, state, n_slots, T.pack.p);
 		gol_amr_collect_kernel<<<xcd_grid((s1 - s0 + kCollectRows - 1) / kCollectRows), kCollectRows, 0, s>>>(
 		    T.pack.p, lst, ptr, nslot, s0, s1, err);
 	} else {

@@ -547,27 +547,25 @@ __global__ void moving_children_kernel(MapCtx m, DevMesh M, const uint64_t* __re
 static void k_moving_children(Grid& g, const uint64_t* dF, size_t nf, std::map<int, std::vector<uint64_t>>& send_ids,
                               std::map<int, std::vector<uint64_t>>& recv_ids, hipStream_t s) {
 	if (!nf) return;
-	DBuf<unsigned long long> cnt;
-	cnt.alloc(1);
+	DevCounter cnt;
+	cnt.word();
 	size_t cap = std::max<size_t>(4096, nf);  // most families do not straddle ranks; once more when short
 	for (int pass = 0; pass < 2; pass++) {
 		DBuf<uint64_t> id;
 		DBuf<int32_t> peer;
 		id.alloc(cap);
 		peer.alloc(cap);
-		HIP_CHECK(hipMemsetAsync(cnt.p, 0, 8, s));
-		moving_children_kernel<<<grid_for(nf, 256), 256, 0, s>>>(g.m, g.dm(), dF, nf, g.rank, id.p, peer.p, cnt.p,
+		moving_children_kernel<<<grid_for(nf, 256), 256, 0, s>>>(g.m, g.dm(), dF, nf, g.rank, id.p, peer.p, cnt.zero(s),
 		                                                        (unsigned long long)cap);
 		HIP_CHECK(hipGetLastError());
-		unsigned long long n = 0;
-		d2h_small(&n, cnt.p, 8, s);
+		const size_t n = cnt.read(s);
 		if (n > cap) {
-			cap = size_t(n);
+			cap = n;
 			continue;
 		}
-		const std::vector<uint64_t> hi = download(id.p, size_t(n), s);
-		const std::vector<int32_t> hp = download(peer.p, size_t(n), s);
-		for (size_t k = 0; k < size_t(n); k++) (hp[k] & 1 ? recv_ids : send_ids)[hp[k] >> 1].push_back(hi[k]);
+		const std::vector<uint64_t> hi = download(id.p, n, s);
+		const std::vector<int32_t> hp = download(peer.p, n, s);
+		for (size_t k = 0; k < n; k++) (hp[k] & 1 ? recv_ids : send_ids)[hp[k] >> 1].push_back(hi[k]);
 		return;
 	}
 	DX_REQUIRE(false, "internal error: moving children beyond their count");
@@ -1204,19 +1202,17 @@ void finish_balance_load_impl(Grid& g) {
 	}
 	DBuf<uint64_t> local;
 	local.alloc(nl + arrived.size() + 1);
-	DBuf<unsigned long long> ctr;
-	ctr.alloc(1);
-	HIP_CHECK(hipMemsetAsync(ctr.p, 0, 8, s));
+	DevCounter ctr;
+	ctr.zero(s);
 	if (nl) {
 		keep_unflagged_kernel<<<unsigned((nl + 256 * kAppendRun - 1) / (256 * kAppendRun)), 256, 0, s>>>(
-		    g.slot_ids.p, flag.p, nl, local.p, ctr.p);
+		    g.slot_ids.p, flag.p, nl, local.p, ctr.d.p);
 		HIP_CHECK(hipGetLastError());
 	}
-	unsigned long long kept = 0;
-	d2h_small(&kept, ctr.p, 8, s);
+	const size_t kept = ctr.read(s);
 	if (!arrived.empty())
 		h2d(local.p + kept, arrived.data(), arrived.size() * 8, s);
-	const size_t n_new = size_t(kept) + arrived.size();
+	const size_t n_new = kept + arrived.size();
 	Mesh nm;
 	mesh_from_local(g, nm, local, n_new);
 	rebuild(g, nm);

@@ -48,10 +48,6 @@ __global__ void select_other_kernel(const uint64_t* ids, const int32_t* own, siz
 
 unsigned select_owner_grid(size_t n) { return unsigned((n + size_t(256) * kAppendRun - 1) / (size_t(256) * kAppendRun)); }
 
-__global__ void fill_owner_kernel(int32_t* own, size_t n, int32_t v) {
-	for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) own[i] = v;
-}
-
 }  // namespace
 
 std::vector<int> HaloPlan::peers() const {
@@ -293,8 +289,7 @@ void mesh_materialize(Grid& g, Mesh& out) {
 	out.kown.alloc(out.n_known + 1);
 	if (c) {
 		HIP_CHECK(hipMemcpyAsync(out.kid.p, local.p, c * 8, hipMemcpyDeviceToDevice, s));
-		fill_owner_kernel<<<grid_for(c, 256), 256, 0, s>>>(out.kown.p, c, g.rank);
-		HIP_CHECK(hipGetLastError());
+		k_fill_i32(out.kown.p, c, g.rank, s);
 	}
 	if (!ring.empty()) {
 		h2d(out.kid.p + c, ring.data(), ring.size() * 8, s);
@@ -333,8 +328,7 @@ void mesh_from_local(Grid& g, Mesh& out, DBuf<uint64_t>& local, size_t n) {
 	out.kown.alloc(out.n_known + 1);
 	if (n) {
 		HIP_CHECK(hipMemcpyAsync(out.kid.p, local.p, n * 8, hipMemcpyDeviceToDevice, s));
-		fill_owner_kernel<<<grid_for(n, 256), 256, 0, s>>>(out.kown.p, n, g.rank);
-		HIP_CHECK(hipGetLastError());
+		k_fill_i32(out.kown.p, n, g.rank, s);
 	}
 	if (!gid.empty()) {
 		h2d(out.kid.p + n, gid.data(), gid.size() * 8, s);
@@ -412,17 +406,14 @@ void rebuild(Grid& g, Mesh& nm) {
 			}
 		} else {
 			d_local.alloc(M.n_known + 1);
-			DBuf<unsigned long long> ctr;
-			ctr.alloc(1);
-			HIP_CHECK(hipMemsetAsync(ctr.p, 0, 8, s));
+			DevCounter ctr;
+			ctr.zero(s);
 			if (M.n_known) {
 				select_owner_kernel<<<select_owner_grid(M.n_known), 256, 0, s>>>(M.kid.p, M.kown.p, M.n_known, g.rank,
-				                                                              d_local.p, ctr.p);
+				                                                              d_local.p, ctr.d.p);
 				HIP_CHECK(hipGetLastError());
 			}
-			unsigned long long hn = 0;
-			d2h_small(&hn, ctr.p, 8, s);
-			g.n_local = size_t(hn);
+			g.n_local = ctr.read(s);
 			if (!g.morton_slots) sort_u64(d_local.p, g.n_local, s);
 		}
 	}
@@ -676,15 +667,11 @@ void rebuild(Grid& g, Mesh& nm) {
 		k_fill_i32(kown.p, nl, g.rank, s);
 		size_t ng = 0;
 		if (M.n_known > nl) {
-			DBuf<unsigned long long> ctr;
-			ctr.alloc(1);
-			HIP_CHECK(hipMemsetAsync(ctr.p, 0, 8, s));
+			DevCounter ctr;
 			select_other_kernel<<<select_owner_grid(M.n_known), 256, 0, s>>>(M.kid.p, M.kown.p, M.n_known, g.rank, kid.p + nl,
-			                                                          kown.p + nl, ctr.p);
+			                                                          kown.p + nl, ctr.zero(s));
 			HIP_CHECK(hipGetLastError());
-			unsigned long long hn = 0;
-			d2h_small(&hn, ctr.p, 8, s);
-			ng = size_t(hn);
+			ng = ctr.read(s);
 		}
 		DX_REQUIRE(nl + ng == M.n_known, "internal error: known leaves are not own + others");
 		M.kid.swap(kid);

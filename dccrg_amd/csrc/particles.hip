@@ -27,7 +27,6 @@
 // No atomic decides a position: a cell's records are its stayers in their
 // previous order, then the arrivals ordered by (source cell id, index in the
 // source cell).
-#include <hipcub/hipcub.hpp>
 
 #include <cmath>
 #include <initializer_list>
@@ -583,8 +582,7 @@ struct ParticleCall {
 		ofirst.alloc(ns + 1);
 		flag.alloc(1);
 		HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, s));
-		record_offsets_kernel<<<grid_for(ns + 1, 256), 256, 0, s>>>(f.voff.p, ns + 1, rec, ofirst.p, flag.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(record_offsets_kernel, ns + 1, s, f.voff.p, ns + 1, rec, ofirst.p, flag.p);
 		int32_t bad = 0;
 		d2h_small(&bad, flag.p, 4, s);
 		DX_REQUIRE(!bad, "a cell's payload is not a multiple of 8 * record_doubles bytes");
@@ -751,36 +749,23 @@ void particles_step(Grid& g, int fid, int K, const double* velocity, double dt, 
 		DBuf<int32_t> iota, order;
 		DBuf<uint64_t> sorted_ids;
 		DBuf<uint32_t> idrank;
-		DBuf<uint8_t> temp;
 		iota.alloc(ns);
 		order.alloc(ns);
 		sorted_ids.alloc(ns);
 		idrank.alloc(ns);
 		k_iota_i32(iota.p, ns, 0, s);
-		size_t tb = 0;
-		HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, g.slot_ids.p, sorted_ids.p, iota.p, order.p, ns, 0,
-		                                             map_id_bits(g.m), s));
-		temp.alloc(tb + 1);
-		HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, g.slot_ids.p, sorted_ids.p, iota.p, order.p, ns, 0,
-		                                             map_id_bits(g.m), s));
-		rank_by_id_kernel<<<grid_for(ns, 256), 256, 0, s>>>(order.p, ns, idrank.p);
-		HIP_CHECK(hipGetLastError());
+		with_temp(cub_sort_pairs(g.slot_ids.p, sorted_ids.p, iota.p, order.p, ns, map_id_bits(g.m), s));
+		launch_per_item(rank_by_id_kernel, ns, s, order.p, ns, idrank.p);
 		keys.alloc(M);
 		keys2.alloc(M);
 		vals.alloc(M);
 		vals2.alloc(M);
-		mover_keys_kernel<<<grid_for(N, 256), 256, 0, s>>>(src.p, dest.p, mover.p, mpos.p, N, idrank.p, bits, keys.p,
-		                                                   vals.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(mover_keys_kernel, N, s, src.p, dest.p, mover.p, mpos.p, N, idrank.p, bits, keys.p, vals.p);
 		const int end_bit = bits + bits_for(nl);
-		tb = 0;
-		HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, keys2.p, vals.p, vals2.p, M, 0, end_bit, s));
-		temp.alloc(tb + 1);
-		HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys.p, keys2.p, vals.p, vals2.p, M, 0, end_bit, s));
+		with_temp(cub_sort_pairs(keys.p, keys2.p, vals.p, vals2.p, M, end_bit, s));
 		// 4. arrivals per destination
-		arrival_runs_kernel<<<grid_for(M, 256), 256, 0, s>>>(keys2.p, M, bits, arr_first.p, arr_end.p);
-		HIP_CHECK(hipGetLastError());
-		HIP_CHECK(hipStreamSynchronize(s));  // temp and the unsorted lists go out of scope
+		launch_per_item(arrival_runs_kernel, M, s, keys2.p, M, bits, arr_first.p, arr_end.p);
+		HIP_CHECK(hipStreamSynchronize(s));  // the unsorted lists go out of scope
 	}
 
 	// 5. new sizes
@@ -788,29 +773,25 @@ void particles_step(Grid& g, int fid, int K, const double* velocity, double dt, 
 	staycnt.alloc(ns + 1);
 	newcnt.alloc(ns + 1);
 	nfirst.alloc(ns + 1);
-	new_counts_kernel<<<grid_for(ns, 256), 256, 0, s>>>(ofirst.p, stayrank.p, arr_first.p, arr_end.p, ns, nl, staycnt.p,
-	                                                    newcnt.p);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(new_counts_kernel, ns, s, ofirst.p, stayrank.p, arr_first.p, arr_end.p, ns, nl, staycnt.p,
+	                newcnt.p);
 	const size_t Nn = scan_exclusive_u32(newcnt.p, nfirst.p, ns, s);
 	DX_REQUIRE(Nn == n_stay + M, "particle counts do not add up");
 	DBuf<uint64_t> noff;
 	noff.alloc(ns + 1);
-	byte_offsets_kernel<<<grid_for(ns + 1, 256), 256, 0, s>>>(nfirst.p, ns + 1, rec, noff.p);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(byte_offsets_kernel, ns + 1, s, nfirst.p, ns + 1, rec, noff.p);
 
 	// 6. scatter into a fresh pool
 	DBuf<uint8_t> nd;
 	nd.alloc(size_t(Nn) * rec + 1);
 	double* out = reinterpret_cast<double*>(nd.p);
 	if (n_stay) {
-		scatter_stayers_kernel<<<grid_for(N, 256), 256, 0, s>>>(a.pool, out, K, N, src.p, stay.p, stayrank.p, ofirst.p,
-		                                                        nfirst.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(scatter_stayers_kernel, N, s, a.pool, out, K, N, src.p, stay.p, stayrank.p, ofirst.p,
+		                nfirst.p);
 	}
 	if (M) {
-		scatter_movers_kernel<<<grid_for(M, 256), 256, 0, s>>>(a.pool, out, K, M, keys2.p, vals2.p, bits, nfirst.p,
-		                                                       staycnt.p, arr_first.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(scatter_movers_kernel, M, s, a.pool, out, K, M, keys2.p, vals2.p, bits, nfirst.p,
+		                staycnt.p, arr_first.p);
 	}
 	uint64_t h[4] = {0, 0, 0, 0};
 	d2h_small(h, dstats.p, sizeof(h), s);  // drains s
@@ -1112,9 +1093,8 @@ bool particles_follow_check(Grid& g, const Field& f) {
 	DBuf<int32_t> flag;
 	flag.alloc(1);
 	HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, s));
-	follow_sizes_ok_kernel<<<grid_for(g.n_local, 256), 256, 0, s>>>(f.voff.p, g.n_local,
-	                                                               uint64_t(f.follow_K) * sizeof(double), flag.p);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(follow_sizes_ok_kernel, g.n_local, s, f.voff.p, g.n_local,
+	                uint64_t(f.follow_K) * sizeof(double), flag.p);
 	int32_t bad = 0;
 	d2h_small(&bad, flag.p, 4, s);
 	return !bad;
@@ -1138,16 +1118,14 @@ void particles_follow_rebuild(Grid& g, Field& f, const uint64_t* old_ids, size_t
 	if (had) {
 		refined.alloc(n_old + 1);
 		rpos.alloc(n_old + 1);
-		follow_classify_kernel<<<grid_for(n_old + 1, 256), 256, 0, s>>>(g.m, newM, old_ids, n_old, nl, src.p, refined.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(follow_classify_kernel, n_old + 1, s, g.m, newM, old_ids, n_old, nl, src.p, refined.p);
 		P = scan_exclusive_u32(refined.p, rpos.p, n_old, s);
 	}
 	DBuf<uint64_t> sizes, noff;
 	sizes.alloc(ns + 1);
 	noff.alloc(ns + 1);
 	if (had) {
-		follow_stay_sizes_kernel<<<grid_for(ns + 1, 256), 256, 0, s>>>(src.p, f.voff.p, ns, sizes.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(follow_stay_sizes_kernel, ns + 1, s, src.p, f.voff.p, ns, sizes.p);
 	} else {
 		HIP_CHECK(hipMemsetAsync(sizes.p, 0, (ns + 1) * 8, s));
 	}
@@ -1159,8 +1137,7 @@ void particles_follow_rebuild(Grid& g, Field& f, const uint64_t* old_ids, size_t
 	if (P) {
 		const uint64_t total = var_total(f, n_old, s);  // the old pool's local part ends at voff[n_old]
 		plist.alloc(P);
-		follow_compact_kernel<<<grid_for(n_old, 256), 256, 0, s>>>(refined.p, rpos.p, n_old, plist.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(follow_compact_kernel, n_old, s, refined.p, rpos.p, n_old, plist.p);
 		child.alloc(size_t(total / rec) + 1);
 		cslot.alloc(8 * P);
 		a.pool = reinterpret_cast<const double*>(f.data.p);
@@ -1198,16 +1175,14 @@ void particles_follow_rebuild(Grid& g, Field& f, const uint64_t* old_ids, size_t
 			rm_dev = up.p;
 		}
 		par.alloc(n_rm);
-		removed_parent_ids_kernel<<<grid_for(n_rm, 256), 256, 0, s>>>(g.m, rm_dev, n_rm, par.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(removed_parent_ids_kernel, n_rm, s, g.m, rm_dev, n_rm, par.p);
 		np = sort_unique_u64(par.p, n_rm, s, map_id_bits(g.m));
 		cidx.alloc(8 * np);
 		pslot.alloc(np);
 		err.alloc(1);
 		HIP_CHECK(hipMemsetAsync(cidx.p, 0xff, 8 * np * sizeof(int32_t), s));
 		HIP_CHECK(hipMemsetAsync(err.p, 0, 4, s));
-		follow_rows_kernel<<<grid_for(n_rm, 256), 256, 0, s>>>(g.m, rm_dev, n_rm, par.p, np, cidx.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(follow_rows_kernel, n_rm, s, g.m, rm_dev, n_rm, par.p, np, cidx.p);
 		k_lookup_slots(par.p, np, newM, pslot.p, err.p, s);  // (a parent without a slot: -1, skipped)
 		follow_parent_sizes_kernel<<<grid_for(np, 256), 256, 0, s>>>(cidx.p, pslot.p, np, nl, f.rm_off.p, rec, sizes.p,
 		                                                             dstats.p);
@@ -2181,9 +2156,8 @@ void particles_create(Grid& g, int fid, int K, int count_field, double count, in
 	err.alloc(2);
 	const uint32_t err0[2] = {0xFFFFFFFFu, 0u};
 	h2d(err.p, err0, sizeof(err0), s);
-	create_counts_kernel<<<grid_for(ns + 1, 256), 256, 0, s>>>(f.voff.p, g.slot_ids.p, ns, nl, rec, F, count, round_random,
-	                                                         k0, k1, sizes.p, err.p);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(create_counts_kernel, ns + 1, s, f.voff.p, g.slot_ids.p, ns, nl, rec, F, count, round_random,
+	                k0, k1, sizes.p, err.p);
 	uint32_t herr[2] = {0, 0};
 	d2h_small(herr, err.p, sizeof(herr), s);
 	DX_REQUIRE(!herr[1], "a cell's payload is not a multiple of 8 * record_doubles bytes");
@@ -2205,8 +2179,7 @@ void particles_create(Grid& g, int fid, int K, int count_field, double count, in
 	DBuf<uint32_t> nfirst, tile_slot;
 	DBuf<CRecipe> drc;
 	nfirst.alloc(nl + 1);
-	create_first_kernel<<<grid_for(nl + 1, 256), 256, 0, s>>>(f.voff.p, noff.p, nl + 1, rec, nfirst.p);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(create_first_kernel, nl + 1, s, f.voff.p, noff.p, nl + 1, rec, nfirst.p);
 	const size_t Nd = size_t(N) * size_t(K);
 	const size_t tiles = (Nd + kCB - 1) / kCB;
 	launch_pass_slots(nfirst.p, nl, size_t(N), tiles, size_t(K), tile_slot, s);

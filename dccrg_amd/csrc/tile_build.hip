@@ -604,8 +604,7 @@ static size_t device_cut(const DBuf<uint8_t>& al, size_t n_inner, size_t n_local
 	const uint32_t* src = next.p;
 	DBuf<uint32_t>* dst = &ja;
 	for (int k = 0; k < 6; k++) {
-		jump_double_kernel<<<grid_for(size_t(n) + 1, 256), 256, 0, s>>>(src, size_t(n) + 1, dst->p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(jump_double_kernel, size_t(n) + 1, s, src, size_t(n) + 1, dst->p);
 		src = dst->p;
 		dst = dst == &ja ? &jb : &ja;
 	}
@@ -652,8 +651,7 @@ TileBuild k_build_tiles(const uint32_t* face_ptr, const int32_t* face_ent, const
 	DBuf<uint8_t> dal;
 	if (morton && n_local) {
 		dal.alloc(n_local);
-		align_kernel<<<grid_for(n_local, 256), 256, 0, s>>>(mc, slot_ids, uint32_t(n_local), dal.p);
-		HIP_CHECK(hipGetLastError());
+		launch_per_item(align_kernel, n_local, s, mc, slot_ids, uint32_t(n_local), dal.p);
 	}
 	DX_LAP("tb.1_align");
 	size_t ntiles = 0;
@@ -737,21 +735,16 @@ TileBuild k_build_tiles(const uint32_t* face_ptr, const int32_t* face_ent, const
 	// then sorted on the bits a (tile, slot) key uses
 	DBuf<uint64_t> all, keys;
 	all.alloc(size_t(n_ent) + 1);
-	ext_keys_kernel<<<grid_for(n_local, 256), 256, 0, s>>>(tg, face_ptr, face_ent, all.p);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(ext_keys_kernel, n_local, s, tg, face_ptr, face_ent, all.p);
 	keys.alloc(size_t(n_ent) + 1);
 	size_t m0 = 0;
 	{
-		DBuf<unsigned long long> nsel;
-		nsel.alloc(1);
-		size_t bytes = 0;
-		HIP_CHECK(hipcub::DeviceSelect::If(nullptr, bytes, all.p, keys.p, nsel.p, size_t(n_ent), OutOfTile(), s));
-		DBuf<uint8_t> temp;
-		temp.alloc(bytes + 1);
-		HIP_CHECK(hipcub::DeviceSelect::If(temp.p, bytes, all.p, keys.p, nsel.p, size_t(n_ent), OutOfTile(), s));
-		unsigned long long h = 0;
-		d2h_small(&h, nsel.p, sizeof(h), s);
-		m0 = size_t(h);
+		DevCounter nsel;
+		nsel.word();
+		with_temp([&](void* t, size_t& b) {
+			return hipcub::DeviceSelect::If(t, b, all.p, keys.p, nsel.d.p, size_t(n_ent), OutOfTile(), s);
+		});
+		m0 = nsel.read(s);
 	}
 	all.release();
 	DX_LAP("tb.3_ext_keys_select");
@@ -759,9 +752,7 @@ TileBuild k_build_tiles(const uint32_t* face_ptr, const int32_t* face_ent, const
 	while (end_bit < 64 && (uint64_t(ntiles) >> (end_bit - 32)) != 0) end_bit++;
 	const size_t m = sort_unique_u64(keys.p, m0, s, end_bit);
 	ext.alloc(m + 1);
-	ext_ranges_kernel<<<grid_for(std::max(m, ntiles + 1), 256), 256, 0, s>>>(keys.p, m, uint32_t(ntiles), ext_ptr.p,
-	                                                                         ext.p);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(ext_ranges_kernel, std::max(m, ntiles + 1), s, keys.p, m, uint32_t(ntiles), ext_ptr.p, ext.p);
 	std::vector<uint32_t> hptr = download(ext_ptr.p, ntiles + 1, s);
 	out.total_ext = m;
 	for (size_t t = 0; t < ntiles; t++) out.max_ext = std::max<size_t>(out.max_ext, hptr[t + 1] - hptr[t]);
@@ -772,12 +763,10 @@ TileBuild k_build_tiles(const uint32_t* face_ptr, const int32_t* face_ent, const
 	DBuf<uint32_t> cnt, fine_idx;
 	cnt.alloc(n_local + 1);
 	fine_idx.alloc(n_local + 1);
-	fine_count_kernel<<<grid_for(n_local, 256), 256, 0, s>>>(uint32_t(n_local), face_ptr, face_ent, cnt.p);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(fine_count_kernel, n_local, s, uint32_t(n_local), face_ptr, face_ent, cnt.p);
 	out.n_fine = scan_exclusive_u32(cnt.p, fine_idx.p, n_local, s);
 	tfine.alloc(2 * out.n_fine + 2);
-	fine_base_kernel<<<grid_for(ntiles, 256), 256, 0, s>>>(tg, fine_idx.p, fine_base.p);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(fine_base_kernel, ntiles, s, tg, fine_idx.p, fine_base.p);
 
 	DX_LAP("tb.5_fine");
 	// 5: tile-local rows
@@ -787,13 +776,11 @@ TileBuild k_build_tiles(const uint32_t* face_ptr, const int32_t* face_ent, const
 	DBuf<uint32_t> ext_ax;
 	ext_ax.alloc(m + 1);
 	HIP_CHECK(hipMemsetAsync(ext_ax.p, 0, (m + 1) * 4, s));
-	tile_ell_kernel<<<grid_for(n_local, 256), 256, 0, s>>>(tg, T, face_ptr, face_ent, ext_ptr.p, ext.p, fine_idx.p,
-	                                                       fine_base.p, tell.p, tfine.p, ext_ax.p, err.p);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(tile_ell_kernel, n_local, s, tg, T, face_ptr, face_ent, ext_ptr.p, ext.p, fine_idx.p,
+	                fine_base.p, tell.p, tfine.p, ext_ax.p, err.p);
 	// ext slots with their axis mask in bits 29..31 (slots < 2^29)
 	ext_pk.alloc(m + 1);
-	pack_ext_kernel<<<grid_for(m, 256), 256, 0, s>>>(ext.p, ext_ax.p, m, ext_pk.p);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(pack_ext_kernel, m, s, ext.p, ext_ax.p, m, ext_pk.p);
 	int herr = 0;
 	d2h_small(&herr, err.p, 4, s);
 	DX_REQUIRE(herr == 0, "internal error: face neighbor missing from its tile's external list");
@@ -940,9 +927,7 @@ __global__ void tile_levels_kernel(const uint8_t* __restrict__ slot_lvl, const u
 void k_tile_levels(const uint8_t* slot_lvl, const uint32_t* ext_pk, size_t n_ext, uint8_t* ext_lvl,
                    RegTileMeta* regmeta, size_t n_reg, hipStream_t s) {
 	const size_t n = std::max(n_ext, n_reg);
-	if (!n) return;
-	tile_levels_kernel<<<grid_for(n, 256), 256, 0, s>>>(slot_lvl, ext_pk, n_ext, ext_lvl, regmeta, n_reg);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(tile_levels_kernel, n, s, slot_lvl, ext_pk, n_ext, ext_lvl, regmeta, n_reg);
 }
 
 }  // namespace dccrgx

@@ -8,7 +8,6 @@
 // sizes (the reference requires the receiver to size its copies first,
 // variable_neighbour_data.cpp:95-102; with that done the bytes are the same).
 // Not a sweep path: copies are one wave per cell.
-#include <hipcub/hipcub.hpp>
 
 #include "dccrgx_internal.hpp"
 
@@ -110,18 +109,6 @@ unsigned wave_grid(size_t n) { return grid_for(n, 4, 8192); }  // 4 waves of 64 
 
 }  // namespace
 
-uint64_t scan_exclusive_u64(const uint64_t* in, uint64_t* out, size_t n, hipStream_t s) {
-	// scans n + 1 entries (in[n] is ignored, out[n] = total)
-	size_t bytes = 0;
-	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n + 1, s));
-	DBuf<uint8_t> temp;
-	temp.alloc(bytes + 1);
-	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp.p, bytes, in, out, n + 1, s));
-	uint64_t h = 0;
-	d2h_small(&h, out + n, sizeof(h), s);
-	return h;
-}
-
 void var_reset(Field& f, size_t n_slots, hipStream_t s) {
 	f.voff.alloc(n_slots + 1);
 	HIP_CHECK(hipMemsetAsync(f.voff.p, 0, (n_slots + 1) * 8, s));
@@ -136,9 +123,7 @@ uint64_t var_total(const Field& f, size_t n_slots, hipStream_t s) {
 }
 
 void var_sizes(const Field& f, const int32_t* slots, size_t slot0, size_t n, uint64_t* out, hipStream_t s) {
-	if (!n) return;
-	var_sizes_kernel<<<grid_for(n, 256), 256, 0, s>>>(f.voff.p, slots, slot0, n, out);
-	HIP_CHECK(hipGetLastError());
+	launch_per_item(var_sizes_kernel, n, s, f.voff.p, slots, slot0, n, out);
 }
 
 void var_relay(Field& f, size_t n_slots, DBuf<uint64_t>& noff, uint64_t total, bool zero, hipStream_t s) {
