@@ -141,6 +141,9 @@ _SIGS = {
     "dccrgx_particles_boris": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
     "dccrgx_particles_create": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, P(C.c_int),
                                           P(C.c_double), u64, P(u64)]),
+    "dccrgx_particles_remove": (C.c_int, [vp, C.c_int, C.c_int, P(C.c_int), P(C.c_double), C.c_int, C.c_int, C.c_int,
+                                          C.c_double, u64, C.c_int, C.c_int, P(C.c_int), P(C.c_int), C.c_int,
+                                          C.c_int, P(u64)]),
     "dccrgx_gradient": (C.c_int, [vp, C.c_int, P(C.c_int), C.c_double, C.c_int]),
     "dccrgx_curl": (C.c_int, [vp, P(C.c_int), P(C.c_int), C.c_double, C.c_int, C.c_int]),
     "dccrgx_divergence": (C.c_int, [vp, P(C.c_int), C.c_int, C.c_double, C.c_int, C.c_int]),

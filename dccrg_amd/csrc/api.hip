@@ -1434,6 +1434,18 @@ int dccrgx_particles_create(dccrgx_grid* gp, int var_field, int record_doubles, 
 	});
 }
 
+int dccrgx_particles_remove(dccrgx_grid* gp, int var_field, int record_doubles, const int* test_i, const double* test_d,
+                            int n_tests, int mask_field, int prob_field, double prob, uint64_t seed, int rescale,
+                            int weight_double, const int* tally_factors, const int* tally_fields, int n_tally,
+                            int into_field, uint64_t stats[4]) {
+	return guard([&] {
+		GRID_OR_FAIL(gp);
+		particles_remove(g, var_field, record_doubles, test_i, test_d, n_tests, mask_field, prob_field, prob, seed,
+		                 rescale, weight_double, tally_factors, tally_fields, n_tally, into_field, stats);
+		return 0;
+	});
+}
+
 // cells_to_send / cells_to_receive while a balance_load is in progress
 // (initialize_balance_load fills them with the migration lists, 3746-3884)
 int dccrgx_get_migration_cells(dccrgx_grid* gp, int peer, int incoming, uint64_t* ids, size_t cap, size_t* n) {

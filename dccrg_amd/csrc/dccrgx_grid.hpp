@@ -152,6 +152,13 @@ void particles_boris(Grid& g, int fid, int K, int e_first, int b_first, int weig
 // number on this process
 void particles_create(Grid& g, int fid, int K, int count_field, double count, int round_random, const int* recipe_i,
                       const double* recipe_d, uint64_t seed, uint64_t* created);
+// dccrgx_particles_remove: the records of the local cells that a mask, a test
+// or chance removes leave their lists (a stable compaction per cell), their
+// moments are tallied per cell and they may be appended to into_fid's lists;
+// stats: kept, removed by mask, by a test, by chance
+void particles_remove(Grid& g, int fid, int K, const int* test_i, const double* test_d, int n_tests, int mask_fid,
+                      int prob_fid, double prob, uint64_t seed, int rescale, int weight_double,
+                      const int* tally_factors, const int* tally_fids, int n_tally, int into_fid, uint64_t stats[4]);
 // n reductions terms[3 j] (DCCRGX_REDUCE_*) over (q * record[terms[3 j + 1]]) *
 // record[terms[3 j + 2]] (-1: 1.0) of the local cells' records into the device
 // doubles d_out, queued on the compute stream; collective: combined over the

@@ -2216,4 +2216,433 @@ void particles_create(Grid& g, int fid, int K, int count_field, double count, in
 	*created = N;
 }
 
+// ---------------------------------------------------------------------------
+// Particles are removed on the device (dccrgx_particles_remove; DESIGN.md
+// "Particles").  The local cells' records are the pool's first N and a cell's
+// kept records keep their order, so the compacted local part is the stable
+// compaction of those N records as one list: the kept records before record r
+// are also the kept records before it in its cell plus those of the cells in
+// front.  Record r lies in chunk r >> 6.
+//   1. decide  - a thread per record (the step's record search names its
+//                cell): mask, tests, chance, the rescale in place.  A wave's
+//                ballot of the kept is the chunk's 64 bits, its popcount the
+//                chunk's count; the verdicts are counted from ballots in the
+//                wave's registers, one partial a wave of the grid;
+//   2. a scan of the chunk counts: kept before r = scanned[r >> 6] +
+//                popcount(bits[r >> 6] below bit r & 63), removed before r =
+//                r - that.  Nothing removed: the call ends here;
+//   3. tally   - a wave per local cell that loses a record: the lanes stride
+//                its records, a butterfly adds the lanes, lane 0 writes;
+//   4. offsets - a thread per slot: kept before the cell's first record times
+//                the record size; a remote copy moves up by the removed bytes;
+//                into_field's cells grow by what their cell loses (varfield's
+//                re-lay puts their own records in front);
+//   5. copy    - a thread per double of the N records, passes of kCB doubles:
+//                a kept double to its rank in the fresh pool, a removed one
+//                (into_field) behind the destination cell's own records, its
+//                cell from the record search.  The remote copies' bytes
+//                follow as one device copy, and the pool is swapped in.
+namespace {
+
+constexpr int kRT = 8;      // tests of one call
+constexpr int kRTally = 4;  // tallies of one call
+
+struct RTest {
+	double lo, hi;
+	int j, mode;  // the tested double; 0 keep inside, 1 drop inside
+};
+
+struct RArgs {
+	double* pool;
+	const uint32_t* ofirst;      // n_local + 1 record offsets of the local slots
+	const uint32_t* chunk_slot;  // passes + 1 (pass_slots_kernel)
+	const uint64_t* slot_ids;
+	const double* M;             // the mask (nullptr: none)
+	const double* F;             // prob_field (nullptr: none)
+	const RTest* tests;
+	uint64_t* kbits;             // per chunk: the kept
+	uint32_t* kcnt;              // per chunk: their number
+	uint32_t* part;              // per wave of the grid: removed by mask, by a test, by chance; rescaled
+	size_t N;
+	double prob;
+	uint32_t K, k0, k1;
+	int n_tests, chance;
+	int wd;  // the double the kept are rescaled in (-1: none)
+};
+
+__global__ __launch_bounds__(kPB) void particles_remove_decide_kernel(const RArgs a) {
+	__shared__ uint32_t s_off[kOffCache];
+	const size_t passes = (a.N + kPB - 1) / kPB;
+	uint32_t n1 = 0, n2 = 0, n3 = 0, ns = 0;  // the wave's counts (one atomic a wave and pass on one word took
+	                                          // 6.9 of (a)'s 7.4 ms in particles_bench --remove)
+	for (size_t t = blockIdx.x; t < passes; t += gridDim.x) {
+		const size_t p = t * kPB + threadIdx.x;
+		const OffsetWindow W = stage_offsets(a.ofirst, a.chunk_slot, t, s_off);
+		int verdict = -1;  // no record
+		bool scaled = false;
+		if (p < a.N) {
+			const size_t c = W.slot(uint32_t(p));
+			double* rec = a.pool + p * a.K;
+			verdict = 0;
+			if (a.M && a.M[c] != 0.0) verdict = 1;
+			for (int k = 0; k < a.n_tests && verdict == 0; k++) {
+				const RTest T = a.tests[k];
+				const double x = rec[T.j];
+				const bool in = T.lo <= x && x < T.hi;
+				if (in == (T.mode == 1)) verdict = 2;
+			}
+			if (a.chance && verdict == 0) {
+				const double pc = a.F ? a.prob * a.F[c] : a.prob;
+				const uint64_t id = a.slot_ids[c];
+				uint32_t w[4];
+				philox4x32_10(uint32_t(id), uint32_t(id >> 32), uint32_t(p) - W.at(c), 0xFFFFFFFEu, a.k0, a.k1, w);
+				const double u = philox_uniform(w[0], w[1]);
+				if (u < pc) {
+					verdict = 3;
+				} else if (a.wd >= 0 && pc > 0.0 && pc < 1.0) {
+					const double rest = 1.0 - pc;
+					rec[a.wd] = rec[a.wd] / rest;
+					scaled = true;
+				}
+			}
+		}
+		const uint64_t kb = __ballot(verdict == 0);
+		const uint64_t b1 = __ballot(verdict == 1), b2 = __ballot(verdict == 2), b3 = __ballot(verdict == 3);
+		const uint64_t bs = __ballot(scaled);
+		if ((threadIdx.x & 63u) == 0) {
+			const size_t ch = t * (kPB >> 6) + (threadIdx.x >> 6);
+			a.kbits[ch] = kb;
+			a.kcnt[ch] = uint32_t(__popcll(kb));
+		}
+		n1 += uint32_t(__popcll(b1));
+		n2 += uint32_t(__popcll(b2));
+		n3 += uint32_t(__popcll(b3));
+		ns += uint32_t(__popcll(bs));
+	}
+	if ((threadIdx.x & 63u) == 0) {
+		uint32_t* part = a.part + 4 * (size_t(blockIdx.x) * (kPB >> 6) + (threadIdx.x >> 6));
+		part[0] = n1;
+		part[1] = n2;
+		part[2] = n3;
+		part[3] = ns;
+	}
+}
+
+// the kept records in front of record r (r <= N: the chunk arrays have an
+// entry past the last record's)
+__device__ __forceinline__ uint32_t kept_before(const uint64_t* __restrict__ kbits, const uint32_t* __restrict__ kbase,
+                                                uint32_t r) {
+	const uint32_t b = r & 63u;
+	return kbase[r >> 6] + uint32_t(__popcll(kbits[r >> 6] & ((1ull << b) - 1ull)));
+}
+
+// (read with unrolled constant indices only, see MArgs)
+struct TArgs {
+	int fu[kRTally], fv[kRTally];  // m_j = (q * record[fu[j]]) * record[fv[j]]; -1: 1.0
+	double* out[kRTally];
+	int n;
+};
+
+__global__ __launch_bounds__(kPB) void particles_remove_tally_kernel(const double* __restrict__ pool,
+                                                                     const uint32_t* __restrict__ ofirst,
+                                                                     const uint64_t* __restrict__ kbits,
+                                                                     const uint32_t* __restrict__ kbase, size_t n_local,
+                                                                     uint32_t K, int wd, const TArgs f) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const size_t waves = size_t(gridDim.x) * (kPB >> 6);
+	for (size_t c = blockIdx.x * size_t(kPB >> 6) + (threadIdx.x >> 6); c < n_local; c += waves) {
+		const uint32_t r0 = ofirst[c], r1 = ofirst[c + 1];
+		if (r1 - r0 == kept_before(kbits, kbase, r1) - kept_before(kbits, kbase, r0)) continue;  // the cell loses none
+		double sum[kRTally] = {};
+		for (uint32_t r = r0 + lane; r < r1; r += 64) {
+			if ((kbits[r >> 6] >> (r & 63u)) & 1ull) continue;
+			const double* rec = pool + size_t(r) * K;
+			const double q = wd < 0 ? 1.0 : rec[wd];
+#pragma unroll
+			for (int j = 0; j < kRTally; j++) {
+				if (j >= f.n) continue;
+				const double u = f.fu[j] < 0 ? 1.0 : rec[f.fu[j]];
+				const double v = f.fv[j] < 0 ? 1.0 : rec[f.fv[j]];
+				const double qu = q * u;
+				const double mj = qu * v;
+				sum[j] = sum[j] + mj;
+			}
+		}
+#pragma unroll
+		for (int j = 0; j < kRTally; j++) {
+			if (j >= f.n) continue;
+			for (int o = 32; o > 0; o >>= 1) sum[j] = sum[j] + __shfl_xor(sum[j], o, 64);
+			if (lane == 0) f.out[j][c] = f.out[j][c] + sum[j];
+		}
+	}
+}
+
+// the byte offsets after the call: var_field's (noff) and into_field's (inoff,
+// nullptr: none)
+__global__ void remove_offsets_kernel(const uint64_t* __restrict__ voff, const uint64_t* __restrict__ ivoff,
+                                      const uint32_t* __restrict__ ofirst, const uint32_t* __restrict__ iofirst,
+                                      const uint64_t* __restrict__ kbits, const uint32_t* __restrict__ kbase,
+                                      size_t n_slots, size_t n_local, uint64_t rec, uint64_t removed,
+                                      uint64_t* __restrict__ noff, uint64_t* __restrict__ inoff) {
+	for (size_t s = blockIdx.x * size_t(blockDim.x) + threadIdx.x; s <= n_slots; s += size_t(gridDim.x) * blockDim.x) {
+		if (s <= n_local) {
+			const uint32_t kr = kept_before(kbits, kbase, ofirst[s]);
+			noff[s] = uint64_t(kr) * rec;
+			if (inoff) inoff[s] = (uint64_t(iofirst[s]) + (ofirst[s] - kr)) * rec;
+		} else {
+			noff[s] = voff[s] - removed * rec;
+			if (inoff) inoff[s] = ivoff[s] + removed * rec;
+		}
+	}
+}
+
+struct XArgs {
+	const double* src;
+	double *dst, *into;         // the fresh pool; into_field's re-laid pool
+	const uint64_t* kbits;
+	const uint32_t* kbase;
+	const uint32_t* ofirst;     // n_local + 1, the source's record offsets
+	const uint32_t* iofirst;    // n_local + 1, into_field's before the call
+	const uint32_t* tile_slot;  // tiles + 1 (pass_slots_kernel)
+	size_t Nd;                  // doubles of the local records
+	uint32_t K;
+};
+
+// The removed records of cell c follow its own in into_field: there the new
+// first record of c is iofirst[c] + (removed before ofirst[c]), so removed
+// record r goes to iofirst[c + 1] + (removed before r).
+template <bool kInto>
+__global__ __launch_bounds__(kCB) void particles_remove_copy_kernel(const XArgs a) {
+	__shared__ uint32_t s_off[kInto ? kOffCache : 1];
+	const size_t tiles = (a.Nd + kCB - 1) / kCB;
+	for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+		const size_t d0 = t * kCB;
+		const size_t r0 = d0 / a.K;  // the same in every lane
+		const uint32_t j0 = uint32_t(d0 - r0 * a.K);
+		OffsetWindow W{};
+		if constexpr (kInto) W = stage_offsets(a.ofirst, a.tile_slot, t, s_off);
+		const size_t d = d0 + threadIdx.x;
+		if (d >= a.Nd) continue;
+		const uint32_t within = j0 + threadIdx.x;
+		const uint32_t dr = within / a.K;
+		const uint32_t j = within - dr * a.K;
+		const uint32_t r = uint32_t(r0) + dr;
+		const uint32_t kr = kept_before(a.kbits, a.kbase, r);
+		if ((a.kbits[r >> 6] >> (r & 63u)) & 1ull) {
+			a.dst[size_t(kr) * a.K + j] = a.src[d];
+		} else if constexpr (kInto) {
+			const size_t c = W.slot(r);
+			a.into[(size_t(a.iofirst[c + 1]) + (r - kr)) * a.K + j] = a.src[d];
+		}
+	}
+}
+
+}  // namespace
+
+void particles_remove(Grid& g, int fid, int K, const int* test_i, const double* test_d, int n_tests, int mask_fid,
+                      int prob_fid, double prob, uint64_t seed, int rescale, int weight_double,
+                      const int* tally_factors, const int* tally_fids, int n_tally, int into_fid, uint64_t stats[4]) {
+	DX_REQUIRE(stats, "null pointer");
+	DX_REQUIRE(g.initialized, "not initialized");
+	Field& f = field(g, fid);
+	DX_REQUIRE(f.var, "particles need a variable-size field (this one is fixed-size)");
+	DX_REQUIRE(K >= 3, "a particle record has at least 3 doubles (the position)");
+	DX_REQUIRE(n_tests >= 0 && n_tests <= kRT, "the number of tests must be 0 .. 8");
+	DX_REQUIRE(!n_tests || (test_i && test_d), "null pointer");
+	std::vector<RTest> tests(size_t(n_tests) + 1);  // (never empty: uploaded as it is)
+	for (int t = 0; t < n_tests; t++) {
+		RTest& T = tests[size_t(t)];
+		T = RTest{test_d[2 * t], test_d[2 * t + 1], test_i[2 * t], test_i[2 * t + 1]};
+		DX_REQUIRE(T.j >= 0 && T.j < K, "test " + std::to_string(t) + " names a double outside 0 .. record_doubles - 1");
+		DX_REQUIRE(T.mode == 0 || T.mode == 1, "a test's mode must be 0 (keep inside) or 1 (drop inside)");
+		DX_REQUIRE(!std::isnan(T.lo) && !std::isnan(T.hi), "a test's bound is NaN");
+	}
+	const double *M = nullptr, *F = nullptr;
+	if (mask_fid != -1) M = reinterpret_cast<const double*>(fp64_cell_field(g, mask_fid, "mask_field").data.p);
+	if (prob_fid != -1) F = reinterpret_cast<const double*>(fp64_cell_field(g, prob_fid, "prob_field").data.p);
+	DX_REQUIRE(std::isfinite(prob), "prob must be finite");
+	require_weight_double(K, weight_double, 3, "position");
+	DX_REQUIRE(!rescale || weight_double != -1, "rescale needs a weight_double");
+	DX_REQUIRE(n_tally >= 0 && n_tally <= kRTally, "the number of tallies must be 0 .. 4");
+	DX_REQUIRE(!n_tally || (tally_factors && tally_fids), "null pointer");
+	TArgs ta{};
+	ta.n = n_tally;
+	for (int j = 0; j < kRTally; j++) {
+		ta.fu[j] = ta.fv[j] = -1;
+		ta.out[j] = nullptr;
+		if (j >= n_tally) continue;
+		ta.fu[j] = tally_factors[2 * j];
+		ta.fv[j] = tally_factors[2 * j + 1];
+		for (int v : {ta.fu[j], ta.fv[j]})
+			DX_REQUIRE(v == -1 || (v >= 3 && v < K),
+			           "a tally factor must be -1 (1.0) or a double of the record past the position (3 <= factor < "
+			           "record_doubles)");
+		ta.out[j] = reinterpret_cast<double*>(fp64_cell_field(g, tally_fids[j], "a tally field").data.p);
+		for (int i = 0; i < j; i++) DX_REQUIRE(tally_fids[i] != tally_fids[j], "two tallies share a field");
+		DX_REQUIRE(tally_fids[j] != mask_fid && tally_fids[j] != prob_fid,
+		           "a tally field is also the mask_field or the prob_field");
+	}
+	Field* fi = nullptr;
+	if (into_fid != -1) {
+		DX_REQUIRE(into_fid != fid, "into_field is the var_field itself");
+		fi = &field(g, into_fid);
+		DX_REQUIRE(fi->var, "into_field must be a variable-size field (this one is fixed-size)");
+	}
+	hipStream_t s = g.s_comp;
+	const size_t ns = g.n_slots, nl = g.n_local;
+	const uint64_t rec = uint64_t(K) * sizeof(double);
+	const uint64_t limit = uint64_t(1) << 31;
+
+	// the record offsets of the local slots; every local cell whole records
+	DBuf<int32_t> flag;
+	flag.alloc(1);
+	auto local_records = [&](const Field& x, DBuf<uint32_t>& of) -> uint64_t {
+		of.alloc(nl + 1);
+		if (!x.voff.p) {
+			HIP_CHECK(hipMemsetAsync(of.p, 0, (nl + 1) * sizeof(uint32_t), s));
+			return 0;
+		}
+		const uint64_t n = var_total(x, nl, s) / rec;
+		DX_REQUIRE(n < limit, "more than 2^31 particles on one process");
+		HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, s));
+		launch_per_item(record_offsets_kernel, nl + 1, s, x.voff.p, nl + 1, rec, of.p, flag.p);
+		int32_t bad = 0;
+		d2h_small(&bad, flag.p, 4, s);
+		DX_REQUIRE(!bad, "a cell's payload is not a multiple of 8 * record_doubles bytes");
+		return n;
+	};
+	DBuf<uint32_t> ofirst, iofirst;
+	uint64_t N = 0;
+	if (ns && nl) {
+		N = local_records(f, ofirst);
+		if (fi) local_records(*fi, iofirst);
+	}
+	if (!N) {
+		for (int k = 0; k < 4; k++) stats[k] = 0;
+		return;
+	}
+	const uint64_t into_bytes = fi && fi->voff.p ? var_total(*fi, ns, s) : 0, into_all = into_bytes / rec;
+
+	// 1. decide, 2. scan.  The rescale writes in place, so where into_field
+	// could overflow the verdicts are counted once without it
+	const size_t passes = (size_t(N) + kPB - 1) / kPB, chunks = passes * (kPB >> 6);
+	DBuf<uint32_t> chunk_slot, kcnt, kbase;
+	DBuf<uint64_t> kbits;
+	DBuf<RTest> dtests;
+	DBuf<uint32_t> part;
+	DBuf<uint64_t> count;
+	launch_pass_slots(ofirst.p, nl, size_t(N), passes, 0, chunk_slot, s);
+	kbits.alloc(chunks + 1);
+	kcnt.alloc(chunks + 1);
+	kbase.alloc(chunks + 1);
+	const unsigned nb = grid_for(passes, 1, 4096);
+	part.alloc(size_t(nb) * (kPB >> 6) * 4);
+	count.alloc(4);
+	dtests.alloc(tests.size());
+	h2d(dtests.p, tests.data(), tests.size() * sizeof(RTest), s);
+	HIP_CHECK(hipMemsetAsync(kbits.p + chunks, 0, sizeof(uint64_t), s));
+	RArgs a{};
+	a.pool = reinterpret_cast<double*>(f.data.p);
+	a.ofirst = ofirst.p;
+	a.chunk_slot = chunk_slot.p;
+	a.slot_ids = g.slot_ids.p;
+	a.M = M;
+	a.F = F;
+	a.tests = dtests.p;
+	a.kbits = kbits.p;
+	a.kcnt = kcnt.p;
+	a.part = part.p;
+	a.N = size_t(N);
+	a.prob = prob;
+	a.K = uint32_t(K);
+	a.k0 = uint32_t(seed);
+	a.k1 = uint32_t(seed >> 32);
+	a.n_tests = n_tests;
+	a.chance = (prob_fid != -1 || prob != 0.0) ? 1 : 0;
+	uint64_t hc[4] = {0, 0, 0, 0};
+	uint64_t kept = 0;
+	auto decide = [&](bool write) {
+		a.wd = write && rescale ? weight_double : -1;
+		k_time_begin(g);
+		particles_remove_decide_kernel<<<nb, kPB, 0, s>>>(a);
+		HIP_CHECK(hipGetLastError());
+		k_time_end(g);
+		sum_parts_kernel<<<1, 256, 0, s>>>(part.p, size_t(nb) * (kPB >> 6), count.p);
+		HIP_CHECK(hipGetLastError());
+		kept = scan_exclusive_u32(kcnt.p, kbase.p, chunks, s);
+		d2h_small(hc, count.p, sizeof(hc), s);
+	};
+	const bool may_overflow = fi && into_all + N >= limit;
+	decide(!may_overflow);
+	const uint64_t removed = N - kept;
+	if (may_overflow) {
+		DX_REQUIRE(into_all + removed < limit, "more than 2^31 - 1 records in into_field afterwards");
+		if (rescale) decide(true);
+	}
+	stats[0] = kept;
+	for (int k = 0; k < 3; k++) stats[k + 1] = hc[k];
+	if (!removed) {
+		if (hc[3]) field_written(f);
+		return;
+	}
+
+	// 3. the tallies, from the pool as it stands
+	if (n_tally) {
+		k_time_begin(g);
+		particles_remove_tally_kernel<<<grid_for(nl, kPB >> 6, 1u << 20), kPB, 0, s>>>(a.pool, ofirst.p, kbits.p,
+		                                                                               kbase.p, nl, a.K, weight_double, ta);
+		HIP_CHECK(hipGetLastError());
+		k_time_end(g);
+		for (int j = 0; j < n_tally; j++) field_written(fixed_field(g, tally_fids[j]));
+	}
+
+	// 4. the new layouts
+	DBuf<uint64_t> noff, inoff;
+	noff.alloc(ns + 1);
+	if (fi) {
+		inoff.alloc(ns + 1);
+		if (!fi->voff.p) var_reset(*fi, ns, s);
+	}
+	launch_per_item(remove_offsets_kernel, ns + 1, s, f.voff.p, fi ? fi->voff.p : nullptr, ofirst.p, iofirst.p, kbits.p,
+	                kbase.p, ns, nl, rec, removed, noff.p, fi ? inoff.p : nullptr);
+	const uint64_t old_total = var_total(f, ns, s), local_bytes = N * rec;
+	const uint64_t total = old_total - removed * rec;
+	DBuf<uint8_t> nd;
+	nd.alloc(total + 1);
+	if (fi) var_relay(*fi, ns, inoff, into_bytes + removed * rec, false, s);
+
+	// 5. the copy; the remote copies' bytes behind the local part
+	XArgs x{};
+	x.src = a.pool;
+	x.dst = reinterpret_cast<double*>(nd.p);
+	x.into = fi ? reinterpret_cast<double*>(fi->data.p) : nullptr;
+	x.kbits = kbits.p;
+	x.kbase = kbase.p;
+	x.ofirst = ofirst.p;
+	x.iofirst = iofirst.p;
+	x.Nd = size_t(N) * size_t(K);
+	x.K = uint32_t(K);
+	const size_t tiles = (x.Nd + kCB - 1) / kCB;
+	DBuf<uint32_t> tile_slot;
+	if (fi) {
+		launch_pass_slots(ofirst.p, nl, size_t(N), tiles, size_t(K), tile_slot, s);
+		x.tile_slot = tile_slot.p;
+	}
+	k_time_begin(g);
+	if (fi)
+		particles_remove_copy_kernel<true><<<grid_for(tiles, 1, 1u << 16), kCB, 0, s>>>(x);
+	else
+		particles_remove_copy_kernel<false><<<grid_for(tiles, 1, 1u << 16), kCB, 0, s>>>(x);
+	HIP_CHECK(hipGetLastError());
+	k_time_end(g);
+	if (old_total > local_bytes)
+		HIP_CHECK(hipMemcpyAsync(nd.p + kept * rec, f.data.p + local_bytes, old_total - local_bytes,
+		                         hipMemcpyDeviceToDevice, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	f.data.swap(nd);
+	f.voff.swap(noff);
+	field_written(f);
+	if (fi) field_written(*fi);
+}
+
 }  // namespace dccrgx

@@ -1070,6 +1070,43 @@ class Dccrg:
                                             int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(made)))
         return int(made.value)
 
+    REMOVE_MODE = {"keep": 0, "drop": 1}
+
+    def particles_remove(self, field, record_doubles, tests=(), mask=None, prob=0.0, prob_field=None, seed=0,
+                         rescale=False, weight=-1, tally=(), into=None):
+        """Removes records from the local cells' lists of the variable float64
+        field `field`, on the device; returns dict(kept=, by_mask=, by_test=,
+        by_chance=).  A record goes by the first stage that holds: `mask` (a
+        float64 Field, cells with a value != 0 absorb), `tests` (each
+        (double, "keep" | "drop", lo, hi): "keep" removes a record whose double
+        is outside [lo, hi), "drop" one inside), chance (u < prob or
+        prob * prob_field[c], u a uniform of (seed, cell id, index in the
+        list)).  rescale=True divides double `weight` of the records chance
+        keeps by 1 - p.  `tally` is a sequence of ((u, v), Field): the Field's
+        cell gains the sum of (q * record[u]) * record[v] over its removed
+        records (q = record[weight], -1 standing for 1.0 everywhere).  `into`
+        is another variable Field that receives the removed records behind
+        its own.  The kept records keep bits and order.  include/dccrgx.h
+        states the operations."""
+        ti, td = [], []
+        for t in tests:
+            j, mode, lo, hi = t
+            ti += [int(j), self.REMOVE_MODE[mode] if isinstance(mode, str) else int(mode)]
+            td += [float(lo), float(hi)]
+        tf, tfl = [], []
+        for (u, v), fl in tally:
+            tf += [int(u), int(v)]
+            tfl.append(fl.id)
+        w = -1 if weight is None else int(weight)
+        st = (C.c_uint64 * 4)()
+        check(lib().dccrgx_particles_remove(
+            self.h, field.id, int(record_doubles), (C.c_int * max(len(ti), 1))(*ti),
+            (C.c_double * max(len(td), 1))(*td), len(ti) // 2, -1 if mask is None else mask.id,
+            -1 if prob_field is None else prob_field.id, float(prob), int(seed) & 0xFFFFFFFFFFFFFFFF,
+            int(bool(rescale)), w, (C.c_int * max(len(tf), 1))(*tf), (C.c_int * max(len(tfl), 1))(*tfl), len(tfl),
+            -1 if into is None else into.id, st))
+        return dict(kept=int(st[0]), by_mask=int(st[1]), by_test=int(st[2]), by_chance=int(st[3]))
+
     def gradient(self, field, out, scale=1.0, region="all", halo=False):
         """out[d] = scale * the d-component of the cell-centred gradient of the
         float64 field `field` in every local cell of `region`; `out` is three

@@ -211,10 +211,16 @@ def main(argv=None):
                    help="Dccrg.particles_create into an empty pool and as an append of one record per cell to the full "
                         "pool (K = 10), beside the host way (NumPy generation and upload) and one re-lay of the pool, "
                         "alternating in one run; writes profiles/particles_bench_create.json unless --out")
+    p.add_argument("--remove", action="store_true",
+                   help="Dccrg.particles_remove on the full pool (K = 10): a velocity test, a mask plane, chance with "
+                        "rescale, a test that removes nothing and the velocity test with `into`, beside one re-lay of "
+                        "the pool and the host route; writes profiles/particles_bench_remove.json unless --out")
     a = p.parse_args(argv)
 
     import torch  # noqa: F401  (one HIP runtime for the process)
 
+    if a.remove:
+        return main_remove(a)
     if a.create:
         return main_create(a)
     if a.reduce:
@@ -1297,6 +1303,136 @@ def main_create(a):
     print(txt, flush=True)
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                 "particles_bench_create.json")
+    with open(out, "w") as f:
+        f.write(txt + "\n")
+
+
+def main_remove(a):
+    """particles_remove on the benchmark's own pool (base^3 cells, ppc records
+    of K = 10, made by particles_create before every timed call): (a) a
+    velocity test that removes about half, (b) a mask slab of one plane of
+    cells, (c) chance 0.5 with rescale, (d) a test that removes nothing, (e)
+    case (a) with `into`; beside them one re-lay of the same pool
+    (VariableField.resize, sizes unchanged) and, once, the host route for (a):
+    flat download, NumPy filter, resize and flat upload."""
+    import dccrg_amd
+    from dccrg_amd._lib import check, lib
+
+    Kb, n = PIC_K, a.base
+    g = dccrg_amd.Dccrg(0, 1, 0).set_initial_length((n, n, n)).set_neighborhood_length(1)
+    g.set_maximum_refinement_level(0).set_periodic(True, True, True).initialize()
+    fld = g.add_variable_field("particles", np.float64, True)
+    other = g.add_variable_field("removed", np.float64, False)
+    ids = g.slot_ids()[: g.n_local]
+    nc = int(ids.size)
+    k = (ids - np.uint64(1)).astype(np.int64)
+    mask = g.add_field("mask", np.float64, False)
+    mask.set((k // (n * n) == n // 2).astype(np.float64))  # one plane of cells
+    recipe = {3: ("normal", 0.0, 0.1), 4: ("normal", 0.0, 0.1), 5: ("normal", 0.0, 0.1), PIC_Q: ("const", 1.0)}
+    N = nc * a.ppc
+    full = np.full(nc, a.ppc * Kb, np.uint64)
+    empty = np.zeros(nc, np.uint64)
+    rec_bytes = Kb * 8
+    inf = float("inf")
+
+    def timed(call):
+        g.synchronize()
+        g.kernel_timing(1)
+        t0 = time.perf_counter()
+        r = call()
+        g.synchronize()
+        dt = (time.perf_counter() - t0) * 1e3
+        kms, kn = g.kernel_timing(0)
+        return dt, (kms if kn else None), r
+
+    def fresh():
+        fld.resize(empty)
+        other.resize(empty)
+        assert g.particles_create(fld, Kb, count=a.ppc, recipe=recipe, seed=1) == N
+
+    cases = {"a_velocity_test_half": dict(tests=[(3, "drop", 0.0, inf)]),
+             "b_mask_plane": dict(mask=mask),
+             "c_chance_half_rescale": dict(prob=0.5, seed=7, rescale=True, weight=PIC_Q),
+             "d_nothing_removed": dict(tests=[(3, "keep", -inf, inf)]),
+             "e_velocity_test_half_into": dict(tests=[(3, "drop", 0.0, inf)], into=other)}
+
+    def host_way():
+        raw = np.empty(N * Kb, np.float64)
+        got = C.c_size_t(0)
+        check(lib().dccrgx_variable_field_download(g.h, fld.id, 0, nc, raw.ctypes.data_as(C.c_void_p), raw.nbytes,
+                                                   C.byref(got)))
+        rec = raw.reshape(nc, a.ppc, Kb)
+        keep = ~(rec[:, :, 3] >= 0.0)
+        kept = np.ascontiguousarray(rec[keep]).reshape(-1)
+        fld.resize(keep.sum(axis=1).astype(np.uint64) * np.uint64(Kb))
+        check(lib().dccrgx_variable_field_upload(g.h, fld.id, 0, nc, kept.ctypes.data_as(C.c_void_p), kept.nbytes))
+        return int(keep.sum())
+
+    runs = {name: dict(host_ms=[], kernel_ms=[]) for name in (*cases, "relay", "host_way")}
+    counts = {}
+    for rnd in range(1 + max(a.repeats, 1)):  # the first round warms up
+        todo = []
+        for name, kw in cases.items():
+            fresh()
+            t = timed(lambda: g.particles_remove(fld, Kb, **kw))
+            counts[name] = t[2]
+            todo.append((name, t))
+        fresh()
+        todo.append(("relay", timed(lambda: fld.resize(full))))
+        if rnd == 1:
+            fresh()
+            t = timed(host_way)
+            assert t[2] == counts["a_velocity_test_half"]["kept"], (t[2], counts)
+            todo.append(("host_way", t))
+        if rnd == 0:
+            continue
+        for name, (dt, kms, _) in todo:
+            runs[name]["host_ms"].append(dt)
+            if kms is not None:
+                runs[name]["kernel_ms"].append(kms)
+    for name, st in counts.items():
+        assert sum(st.values()) == N, (name, st)
+    assert counts["d_nothing_removed"]["kept"] == N and counts["b_mask_plane"]["by_mask"] == n * n * a.ppc
+    g.close()
+    res = {}
+    for name, r in runs.items():
+        res[name] = dict(host_ms=float(np.median(r["host_ms"])), host_runs_ms=r["host_ms"])
+        if r["kernel_ms"]:
+            res[name].update(kernel_ms=float(np.median(r["kernel_ms"])), kernel_runs_ms=r["kernel_ms"])
+    relay, host = res["relay"]["host_ms"], res["host_way"]["host_ms"]
+    chunks = (N + 63) // 64
+    for name, kw in cases.items():
+        st, r = counts[name], res[name]
+        kept = st["kept"]
+        removed = N - kept
+        # the decision: one tested double per record (its 64-byte line is what HBM moves; the double is counted),
+        # a mask or no field, the chunk bits and counts; (c) also reads and writes the weight of the kept
+        decide = N * 8 * (1 if kw.get("tests") else 0) + (nc * 8 if "mask" in kw else 0) + chunks * 12
+        if kw.get("rescale"):
+            decide += 2 * 8 * kept
+        moved = 0 if not removed else 2 * kept * rec_bytes + (2 * removed * rec_bytes if "into" in kw else 0)
+        r.update(counts=st, decide_bytes=decide, copy_bytes=moved, alg_bytes=decide + moved,
+                 over_relay=r["host_ms"] / relay, over_host_way=r["host_ms"] / host,
+                 frac_of_peak_whole_call=(decide + moved) / (r["host_ms"] / 1e3) / 1e9 / PEAK_HBM_GBS)
+        if "kernel_ms" in r:
+            r["frac_of_peak_kernels"] = (decide + moved) / (r["kernel_ms"] / 1e3) / 1e9 / PEAK_HBM_GBS
+    ra = res["a_velocity_test_half"]
+    line = {"metric": "particles_remove", "value": N / (ra["host_ms"] / 1e3), "unit": "records/s", "n_gpus": 1,
+            "steps": a.repeats, "warmup": 1, "higher_is_better": True, "dtype": "fp64",
+            "config": {"workload": f"{n}^3 periodic cells, {a.ppc} records of K = {Kb} per cell from particles_create "
+                                   "before every timed call; host_ms: the synchronized host clock around the whole call "
+                                   "(checks, scans, the fresh pool and the swap included); kernel_ms: between device "
+                                   "events around the decide, tally and copy kernels; relay: VariableField.resize of "
+                                   "the same pool, sizes unchanged; host_way: case (a) by a flat download, a NumPy "
+                                   "filter, resize and a flat upload, timed once; alg_bytes: the decision's reads, the "
+                                   "kept records read and written once (and the removed ones with into), no remote "
+                                   "part on one process",
+                       "cells": nc, "records": N, "record_bytes": rec_bytes},
+            **{name: res[name] for name in cases}, "relay": res["relay"], "host_way": res["host_way"]}
+    txt = json.dumps(line)
+    print(txt, flush=True)
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "particles_bench_remove.json")
     with open(out, "w") as f:
         f.write(txt + "\n")
 

@@ -1262,6 +1262,56 @@ public:
 		                                      count, round_random ? 1 : 0, ri.data(), rd.data(), seed, &created));
 		return created;
 	}
+	// a test of particles_remove on one double of a record: KEEP removes the
+	// record when the double is outside [lo, hi), DROP when it is inside (a
+	// NaN is outside; infinite bounds give one-sided tests)
+	struct Remove_Test {
+		enum Mode { KEEP = 0, DROP = 1 };
+		int record_double;
+		Mode mode;
+		double lo, hi;
+	};
+	// a tally of particles_remove: field[c] += the sum of (q u) v over the
+	// records removed from c, u and v doubles of the record or -1 for 1.0
+	struct Remove_Tally {
+		int u, v;
+		const Device_Field<double>* field;
+	};
+	// records leave the local cells' lists on the device, by the first of:
+	// mask[c] != 0, a test, chance (u < prob or prob * prob_field[c], u a
+	// uniform of (seed, cell id, index in the list)); rescale divides double
+	// weight_double of the records chance keeps by 1 - p.  The kept records
+	// keep bits and order; the removed ones are tallied per cell and appended
+	// to `into`'s lists when given (dccrgx.h has the operations).  Returns
+	// {kept, removed by mask, by a test, by chance} of this process.
+	std::array<uint64_t, 4> particles_remove(const Device_Variable_Field<double>& particles, const int record_doubles,
+	                                         const std::vector<Remove_Test>& tests = {},
+	                                         const Device_Field<double>* mask = nullptr, const double prob = 0.0,
+	                                         const Device_Field<double>* prob_field = nullptr, const uint64_t seed = 0,
+	                                         const bool rescale = false, const int weight_double = -1,
+	                                         const std::vector<Remove_Tally>& tally = {},
+	                                         const Device_Variable_Field<double>* into = nullptr) {
+		std::vector<int> ti(2 * tests.size() + 1, 0), tf(2 * tally.size() + 1, -1), tfl(tally.size() + 1, -1);
+		std::vector<double> td(2 * tests.size() + 1, 0.0);
+		for (size_t t = 0; t < tests.size(); t++) {
+			ti[2 * t] = tests[t].record_double;
+			ti[2 * t + 1] = int(tests[t].mode);
+			td[2 * t] = tests[t].lo;
+			td[2 * t + 1] = tests[t].hi;
+		}
+		for (size_t j = 0; j < tally.size(); j++) {
+			if (!tally[j].field) throw std::invalid_argument("particles_remove: a tally without a field");
+			tf[2 * j] = tally[j].u;
+			tf[2 * j + 1] = tally[j].v;
+			tfl[j] = tally[j].field->id();
+		}
+		std::array<uint64_t, 4> st{{0, 0, 0, 0}};
+		detail::check(dccrgx_particles_remove(g_, particles.id(), record_doubles, ti.data(), td.data(), int(tests.size()),
+		                                      mask ? mask->id() : -1, prob_field ? prob_field->id() : -1, prob, seed,
+		                                      rescale ? 1 : 0, weight_double, tf.data(), tfl.data(), int(tally.size()),
+		                                      into ? into->id() : -1, st.data()));
+		return st;
+	}
 	// particles -> a cell field: out[c] = the sum of q W(p, c) over the records
 	// of the local cell c and of the distinct leaves of its neighbors_of
 	// (copies of remote neighbors included: update them first); q = double

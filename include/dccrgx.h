@@ -622,6 +622,72 @@ int dccrgx_particles_boris(dccrgx_grid* g, int var_field, int record_doubles, in
 int dccrgx_particles_create(dccrgx_grid* g, int var_field, int record_doubles /* K */, int count_field, double count,
                             int round_random, const int* recipe_i /* 3 K: kind, base_field, spread_field */,
                             const double* recipe_d /* 2 K: a, b */, uint64_t seed, uint64_t* created);
+/* remove: records leave the lists of the local cells, on the device; the
+ * counterpart of create.  Remote copies keep their bytes and sizes.
+ *
+ * The decision, for the record with index i in the list of local cell c as
+ * the list stands before the call: it is removed by the first stage that
+ * holds, else kept.
+ *   1. mask: mask_field != -1 is a fixed fp64 field M; removed when
+ *      M[c] != 0.0 (a NaN absorbs, -0.0 does not).
+ *   2. tests t = 0 .. n_tests - 1 (0 <= n_tests <= 8): x = record[test_i[2 t]]
+ *      (any double 0 <= j < K), in = (lo_t <= x) && (x < hi_t) with
+ *      lo_t, hi_t = test_d[2 t], test_d[2 t + 1]: a NaN x is not in, infinite
+ *      bounds give one-sided tests, lo == hi is the empty interval.  Mode
+ *      test_i[2 t + 1]: 0 (keep inside) removes when !in, 1 (drop inside)
+ *      removes when in.
+ *   3. chance, active when prob_field != -1 || prob != 0.0: p_c = prob, or
+ *      prob * F[c] (one product; F a fixed fp64 field).  u = the first uniform
+ *      (create's words-to-double rule) of the Philox4x32-10 block with key =
+ *      (seed's low word, seed's high word) and counter (id low, id high, i,
+ *      0xFFFFFFFE); removed when u < p_c, so p_c <= 0 or NaN removes nothing
+ *      and p_c >= 1 everything.  i is the index before the call whatever
+ *      stages 1 and 2 removed; no block is computed for a record an earlier
+ *      stage removed.  The verdict is a function of (seed, cell id, i, the
+ *      record, the cell's field values) alone.
+ * rescale != 0 (needs weight_double != -1): a record that reaches stage 3 and
+ * is kept, in a cell with 0 < p_c < 1, gets
+ *   rest = 1.0 - p_c;  record[w] = record[w] / rest
+ * (one difference, one quotient).  Nothing else of a kept record is written;
+ * a cell's kept records keep their bits and their relative order.
+ *
+ * Tallies j = 0 .. n_tally - 1 (0 <= n_tally <= 4), of a removed record:
+ *   m_j = (q * u) * v, q = record[weight_double] (1.0 with -1), u, v =
+ *   record[tally_factors[2 j]], record[tally_factors[2 j + 1]] (-1: 1.0), each
+ *   product rounded as in dccrgx_particles_deposit_moments;
+ *   T_j[c] = T_j[c] + S_j(c), S_j(c) the sum of m_j over the records removed
+ *   from c by any stage, T_j the fixed fp64 field tally_fields[j].  The order
+ *   of the sum is unspecified but fixed (no atomic decides it): two calls on
+ *   equal states give equal bits.  A cell that loses no record is not written;
+ *   remote-copy slots never are.  Factors (-1, -1) collect the absorbed
+ *   charge, (3, -1) a momentum, (3, 3) an energy component.
+ *
+ * into_field: -1 discards the removed records.  Otherwise another variable
+ * field whose local cells hold whole records of the same K: the records
+ * removed from c are appended behind c's records there, in the order they had
+ * in the source list, bits unchanged.  Its remote copies are untouched.
+ *
+ * stats = {kept, removed by mask, removed by a test, removed by chance}, the
+ * totals of this process's local cells.  A call that removes nothing and
+ * rescales nothing changes nothing (no write is recorded, no pool is built).
+ * A field with no pool, or no local cells: zeros.
+ *
+ * DCCRGX_EINVAL, before any change and with stats untouched: a fixed-size
+ * var_field or into_field; K < 3; a local cell of either pool whose bytes are
+ * no multiple of 8 K; n_tests outside 0..8; a tested double outside [0, K); a
+ * mode other than 0, 1; a NaN lo or hi; a mask_field, prob_field or tally
+ * field that is neither -1 (where allowed) nor a fixed 8-byte field; prob not
+ * finite; rescale without weight_double; weight_double neither -1 nor in
+ * [3, K); a tally factor neither -1 nor in [3, K); n_tally outside 0..4; two
+ * equal tally fields; a tally field equal to mask_field or prob_field;
+ * into_field == var_field; more than 2^31 - 1 records in into_field
+ * afterwards. */
+int dccrgx_particles_remove(dccrgx_grid* g, int var_field, int record_doubles /* K */,
+                            const int* test_i /* 2 n_tests: double, mode */,
+                            const double* test_d /* 2 n_tests: lo, hi */, int n_tests, int mask_field, int prob_field,
+                            double prob, uint64_t seed, int rescale, int weight_double,
+                            const int* tally_factors /* 2 n_tally */, const int* tally_fields /* n_tally */,
+                            int n_tally, int into_field, uint64_t stats[4]);
 /* The cell-centred gradient of the fixed fp64 field in_field over the leaves:
  * out_fields[d] (fixed fp64 fields, -1: component not wanted) of every local
  * cell of `region` (DCCRGX_REGION_*; inner then outer writes the bits of all)
