@@ -134,6 +134,12 @@ inline unsigned alloc_skew_next() {
 // capacity (what pool_free must be given back).
 void* pool_alloc(size_t bytes, size_t& capacity);
 void pool_free(void* raw, size_t capacity);
+// Test mode, DCCRGX_POOL_POISON=<0..255> (read at every call; unset or empty
+// is off and costs the getenv alone): every byte of a block holds that value
+// when pool_alloc hands it out and again once it is released, both complete on
+// return (device synchronisations).  pool_poison refills a block in use the
+// same way and does nothing when the mode is off.
+void pool_poison(void* raw, size_t capacity);
 
 template <class T>
 struct DBuf {
@@ -172,8 +178,13 @@ struct DBuf {
 		raw = nullptr;
 		cap = 0;
 	}
+	// contents undefined (the test mode fills them, a kept block included);
+	// what must survive goes through reserve
 	void alloc(size_t count) {
-		if (count == n && p) return;
+		if (count == n && p) {
+			pool_poison(raw, cap);
+			return;
+		}
 		release();
 		if (count) {
 			const size_t skew = count * sizeof(T) >= (size_t(1) << 20) ? size_t(alloc_skew_next()) * 4352u : 0;

@@ -110,6 +110,10 @@ __global__ __launch_bounds__(64 * G3_ROWS) void gol_structured_yr(const uint32_t
 			if (py) y -= ny;
 			else in = false;
 		}
+		// row i feeds the output rows max(0, i - 2) .. min(i, YR - 1): absent
+		// when the first of them is (the one subtraction above leaves y >= ny
+		// for ny == 1: a row past the plane)
+		if (y0 + max(0, i - 2) >= ny) in = false;
 		rin[i] = in;
 		orow[i] = in ? size_t(y) * nx : 0;
 	}

@@ -89,19 +89,53 @@ void free_all(Pool& P) {
 	P.held = 0;
 }
 
+// DCCRGX_POOL_POISON=<0..255>: the test mode's fill byte, or -1 when unset,
+// empty or no such number.  Read at every call (as DCCRGX_APPEND_CAP is), so
+// a test can switch it inside one process.
+int poison_byte() {
+	const char* e = std::getenv("DCCRGX_POOL_POISON");
+	if (!e || !*e) return -1;
+	char* end = nullptr;
+	const unsigned long v = std::strtoul(e, &end, 10);
+	return end == e || *end || v > 255 ? -1 : int(v);
+}
+
+// every byte of the block holds `byte` on return: the grids' streams do not
+// wait for the null stream and the pool does not know the caller's, so the
+// fill is waited for here
+void fill(void* raw, size_t cap, int byte) {
+	HIP_CHECK(hipMemset(raw, byte, cap));
+	HIP_CHECK(hipDeviceSynchronize());
+}
+
 }  // namespace
 
+void pool_poison(void* raw, size_t cap) {
+	const int b = poison_byte();
+	if (b < 0 || !raw || !cap) return;
+	// queued work of the caller may still read or write the block
+	HIP_CHECK(hipDeviceSynchronize());
+	fill(raw, cap, b);
+}
+
 void* pool_alloc(size_t bytes, size_t& cap) {
+	const int poison = poison_byte();
 	const size_t want = size_class(bytes);
 	Pool& P = pool();
 	std::lock_guard<std::mutex> lock(P.mu);
 	void* out = nullptr;
-	if (take(P, P.ready, want, out, cap)) return out;
+	if (take(P, P.ready, want, out, cap)) {
+		if (poison >= 0) fill(out, cap, poison);
+		return out;
+	}
 	{
 		auto it = P.pending.lower_bound(want);
 		if (it != P.pending.end() && (want <= kBig ? it->first == want : it->first <= want + want / 4)) {
 			retire_pending(P);
-			if (take(P, P.ready, want, out, cap)) return out;
+			if (take(P, P.ready, want, out, cap)) {
+				if (poison >= 0) fill(out, cap, poison);
+				return out;
+			}
 		}
 	}
 #if DCCRGX_PHASE_TIMING
@@ -122,11 +156,20 @@ void* pool_alloc(size_t bytes, size_t& cap) {
 		                             hipGetErrorString(e));
 	}
 	cap = want;
+	if (poison >= 0) fill(out, cap, poison);
 	return out;
 }
 
 void pool_free(void* raw, size_t cap) {
 	if (!raw) return;
+	// test mode: a pointer kept past its buffer's life reads the fill byte
+	// (queued work may still use the block: drained first; no throw, buffers
+	// are released by destructors, some after the runtime has gone)
+	if (const int b = poison_byte(); b >= 0) {
+		if (hipDeviceSynchronize() != hipSuccess || hipMemset(raw, b, cap) != hipSuccess ||
+		    hipDeviceSynchronize() != hipSuccess)
+			(void)hipGetLastError();
+	}
 	Pool& P = pool();
 	std::lock_guard<std::mutex> lock(P.mu);
 	if (P.held + cap > max_held()) {

@@ -40,7 +40,14 @@ def _run(g, o, steps):
                                              ((2, 3, 1), (True, True, False)), ((64, 8, 40), (False, True, False)),
                                              # 256-multiples of x: the 16-B-per-lane kernel
                                              ((256, 8, 12), (False, False, False)), ((256, 6, 9), (True, True, True)),
-                                             ((512, 5, 40), (True, False, False)), ((256, 1, 1), (True, True, True))])
+                                             ((512, 5, 40), (True, False, False)), ((256, 1, 1), (True, True, True)),
+                                             # fewer rows than a wave's two, on more than one plane
+                                             ((256, 1, 3), (True, True, True)),
+                                             # three z chunks of 64 planes: one starts past 0 and ends before nz
+                                             ((256, 3, 130), (True, True, True)),
+                                             ((256, 3, 130), (False, False, False)),
+                                             # odd ny wrapped in y, two x segments
+                                             ((512, 5, 3), (True, True, True))])
 def test_structured_matches_oracle(gpu, length, periodic):
     g, o = make_pair(length, 0, periodic, 1)
     got, exp = _run(g, o, 6)
